@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- frames/s of the quantized per-agent encode + intermediate-fusion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--inflight F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--inflight F] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -820,6 +820,55 @@ def cpu_baseline_torch(fp_model, qt, sc_np, cores, warmup=3, timed=10):
     return out
 
 
+DUMP_MAX_BYTES = 60 << 20                  # --dump-outputs: all arrays together (headers aside) stay under 64 MB
+DUMP_STEP = 2654435761                     # prime, above any dumped array's element count: i -> i * DUMP_STEP mod n permutes 0 .. n-1
+
+
+def dump_sample_indices(n, k, device="cpu"):
+    """``k`` distinct flat indices into an array of ``n`` elements, sorted: ``{i * DUMP_STEP mod n : 0 <= i < k}``.  Integer arithmetic
+    only, so the sample is the same on every host and library version; DUMP_STEP is a prime larger than ``n``, so the map is one-to-one
+    and its values spread over the whole array."""
+    import torch
+    if not 0 <= k <= n < DUMP_STEP:
+        raise ValueError(f"dump_sample_indices: need 0 <= k <= n < {DUMP_STEP}, got n = {n}, k = {k}")
+    return torch.sort(torch.arange(k, dtype=torch.int64, device=device) * DUMP_STEP % n).values
+
+
+def dump_outputs(out, outdir):
+    """``--dump-outputs DIR``: the arrays of the output dict a caller of the timed path receives, as ``DIR/<name>.npy`` (float32; a float64
+    output stays float64).  An array that is a view into another array of the dict spanning all of its storage (``cls_preds``,
+    ``reg_preds`` and ``dir_preds`` are slices of ``preds_tensor``) is not written: its elements are in that array's file.  When the rest
+    exceeds DUMP_MAX_BYTES, every array is written as the same fraction of its elements, at the flat (C-order) indices of
+    ``dump_sample_indices`` -- the same for the same shape in every run, so two builds compare element for element.
+    Returns {name: [full shape, elements written]} and, for a view left out, {name: "in <array>.npy"}."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: v.detach() for k, v in sorted(out.items()) if isinstance(v, torch.Tensor)}
+
+    def spans_storage(t):
+        return t.is_contiguous() and t.numel() * t.element_size() == t.untyped_storage().nbytes()
+    written, keep = {}, {}
+    for name, t in arrays.items():
+        whole = [m for m, u in arrays.items() if m != name and spans_storage(u) and not spans_storage(t)
+                 and u.untyped_storage().data_ptr() == t.untyped_storage().data_ptr()]
+        if whole:
+            written[name] = f"in {whole[0]}.npy"
+        else:
+            keep[name] = t if t.dtype == torch.float64 else t.float()
+    total = sum(t.numel() * t.element_size() for t in keep.values())
+    for name, t in keep.items():
+        n = t.numel()
+        k = n if total <= DUMP_MAX_BYTES else n * DUMP_MAX_BYTES // total
+        if k < n:
+            a = t.reshape(-1)[dump_sample_indices(n, k, t.device)].cpu().numpy()
+        else:
+            a = t.cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        written[name] = [list(t.shape), int(k)]
+    return written
+
+
 def self_launch(n, argv, check_devices=True):
     """``python bench.py --gpus N`` without a launcher: start ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` as a
     FRESH CHILD (this process has not touched a GPU: counting devices does not initialise one, and a process that did must never
@@ -1014,7 +1063,14 @@ def main():
                          "every-rank-is-its-own-ego mode execute); default 0")
     ap.add_argument("--dry-run-ranks", action="store_true",
                     help="launcher check (CPU, gloo): every rank joins the group, rank 0 prints a line with n_gpus = world size; no GPU work")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output arrays of the last timed step (rank 0) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (a fixed sample of larger arrays; bench_dump/ is git-ignored): the same arguments give the same inputs in every run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.rehearse_world or args.dry_run_ranks):
+        ap.error("--dump-outputs writes the outputs of the timed steps of the main line: not with --rehearse-world or --dry-run-ranks")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_run_ranks):
         # a bare `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU) and relay rank 0's line
@@ -1079,7 +1135,7 @@ def main():
             i = it[0] % F
             it[0] += 1
             with torch.cuda.stream(streams[i]):
-                reps[i]()
+                return reps[i]()
         launch = f"hipGraph replay of a {B}-frame batch, {F} batches in flight on {F} streams"
         frames_per_step = B
     else:
@@ -1110,7 +1166,7 @@ def main():
                 i = k[0] % F
                 k[0] += 1
                 with torch.cuda.stream(streams[i]):
-                    shardeds[i].forward(mine, pose)
+                    return shardeds[i].forward(mine, pose)
             return step, shardeds
         step, shardeds = make_step(args.ego_only)
         link_txt = "torch.distributed nccl = RCCL" if args.link == "torch" else "qv2x_allgather_codes (RCCL)"
@@ -1126,13 +1182,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    last_out = [None]                    # the output dict the latest timed step returned (--dump-outputs)
+
     def timed(step_fn, warmup, steps):
         for _ in range(warmup):
             step_fn()
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step_fn()
+            last_out[0] = step_fn()
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -1142,6 +1200,10 @@ def main():
         return dt
 
     dt = timed(step, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the device: the later measurements reuse engine 0's workspace
+        written = dump_outputs(last_out[0], args.dump_outputs)
+        print(f"[bench] wrote the last timed step's outputs to {args.dump_outputs}: " + json.dumps(written), file=sys.stderr, flush=True)
     if sharded_mode and not args.ego_only:
         # the parity configuration of SURVEY 8(e)(i) beside the headline: only rank 0 fuses -- its output is the single-process model's
         del shardeds

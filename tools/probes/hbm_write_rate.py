@@ -1,5 +1,5 @@
-import torch, sys
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import bench
 x = torch.empty(414_515_200 // 4, dtype=torch.float32, device="cuda")
 y = torch.empty_like(x)
