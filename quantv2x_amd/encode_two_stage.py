@@ -160,7 +160,8 @@ def candidate_tables(state: Dict[str, np.ndarray], levels: int, in_delta: float,
         d = ((rest + 128) % 256) - 128
         limbs.append(d.astype(np.int8))
         rest = (rest - d) // 256
-    assert not rest.any()
+    if rest.any():
+        raise ValueError("two-stage encode: G on the grid does not fit the candidate stage's int8 limbs")
     bias = np.rint(gb / h).astype(np.int64) + (128 - int(in_zx)) * gi.sum(1)
     tables = np.stack([np.rint(tabs[(l, j)] / h) for l in range(levels) for j in range(l)]) if levels > 1 else np.zeros((1, kc, kc))
     if np.abs(tables).max() >= 2 ** 28 or np.abs(bias).max() >= 2 ** 44:          # (the kernel adds two table entries to 256 a1 + a0 in i32)

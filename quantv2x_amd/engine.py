@@ -264,6 +264,83 @@ class _Heads:
         self.lut_tables = (_dev(t.astype(np.float32), dev), _dev(b.astype(np.float32), dev))
 
 
+# ---- shared by every deployed engine ------------------------------------------------------------------------------------------------
+def scene_layout(data_dict: dict, n_total: int):
+    """``(pairwise f64 contiguous, agents per scene)`` of one model call: ``record_len`` is read on the host (its values shape the launch
+    list), so a device ``record_len`` is refused during HIP-graph capture (``capture_forward`` hands the forward a CPU copy)."""
+    pairwise = data_dict["pairwise_t_matrix"]
+    if pairwise.dtype != torch.float64 or not pairwise.is_contiguous():
+        pairwise = pairwise.to(torch.float64).contiguous()
+    if pairwise.shape[0] == 1:
+        return pairwise, [n_total]
+    rl = data_dict["record_len"]
+    if isinstance(rl, torch.Tensor) and rl.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise ValueError("record_len on the GPU cannot be read during HIP-graph capture: pass a CPU tensor")
+    return pairwise, [int(v) for v in (rl.tolist() if isinstance(rl, torch.Tensor) else rl)]
+
+
+def split_heads(preds: torch.Tensor, splits, suffix: str = "") -> dict:
+    """cls | reg | dir as views of the stacked predictions ``preds`` [n, C, H, W] (plus ``preds_tensor`` itself without a suffix)."""
+    c, r, _ = splits
+    out = {"cls_preds" + suffix: preds[:, :c], "reg_preds" + suffix: preds[:, c:c + r], "dir_preds" + suffix: preds[:, c + r:]}
+    if not suffix:
+        out["preds_tensor"] = preds
+    return out
+
+
+def capture_forward(module: nn.Module, data_dict: dict):
+    """Capture one ``module.forward(data_dict)`` into a HIP graph (torch.cuda.CUDAGraph on ROCm) after two warm-up forwards on a side stream.
+    The returned callable replays it on the same input tensors (refresh their contents in place between replays) and returns the same
+    output dict; ``replay.graph`` is the graph.  A device ``record_len`` is replaced by a CPU copy: its values shape the launch list."""
+    rl = data_dict.get("record_len")
+    if data_dict["pairwise_t_matrix"].shape[0] > 1 and isinstance(rl, torch.Tensor) and rl.is_cuda:
+        data_dict = dict(data_dict, record_len=rl.cpu())
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            module.forward(data_dict)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = module.forward(data_dict)
+
+    def replay():
+        graph.replay()
+        return out
+    replay.graph = graph
+    return replay
+
+
+def assemble_heter_codes(owner: str, engines: dict, slot_cache: dict, agents: list, data_dict: dict, encode, taps: Optional[dict]) -> torch.Tensor:
+    """The code planes u8 [levels, n * H*W] of a heterogeneous scene in agent order: every modality's engine encodes its own agents
+    (``encode(engine, inputs, k, taps)``) and ``index_copy_`` puts them in their slots.  The slot indices are an H2D copy: built once per
+    agent layout in ``slot_cache``, refused during HIP-graph capture (``capture_forward`` runs eager forwards first)."""
+    unknown = sorted(set(agents) - set(engines))
+    if unknown:
+        raise NotImplementedError(f"{owner}: no engine for modality {unknown}")
+    slots = slot_cache.get(tuple(agents))
+    if slots is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.Qv2xError(f"{owner}: agent layout {agents} is new and the stream is capturing -- its slot indices are an H2D copy; "
+                              "run one eager forward of this layout first (capture does)")
+        slots = {m: torch.as_tensor([i for i, a in enumerate(agents) if a == m], dtype=torch.int64, device=e.dev) for m, e in engines.items()}
+        slot_cache[tuple(agents)] = slots
+    e = next(iter(engines.values()))                                 # (every modality's feature map and code planes are the same size)
+    n_total, hw, lv = len(agents), e.fh * e.fw, e.levels
+    enc = torch.empty((lv, n_total * hw), dtype=torch.uint8, device=e.dev)
+    for m, eng in engines.items():
+        k = int(slots[m].numel())
+        if not k:
+            continue
+        mt = {} if taps is not None else None
+        codes = encode(eng, data_dict["inputs_" + m], k, mt).view(lv, k, hw)
+        enc.view(lv, n_total, hw).index_copy_(1, slots[m], codes)                                # agent order (a copy, no arithmetic)
+        if taps is not None:
+            taps["modality/" + m] = mt
+    return enc
+
+
 class DeployedModel(nn.Module):
     """The hot path as HIP kernels.  Same call contract as the reference's model."""
     # a7-a11 as ONE launch (qv2x_fuse_heads_batch_f32: the fused map stays in LDS) from this many 32-cell tiles on -- four rounds of the
@@ -280,24 +357,8 @@ class DeployedModel(nn.Module):
 
     def __init__(self, state: Dict[str, np.ndarray], device="cuda", emit_single_preds: Optional[bool] = None):
         super().__init__()
-        self.lib = L.load()                      # raises if libqv2x.so is absent: no fallback
-        if not torch.cuda.is_available():
-            raise L.Qv2xError("DeployedModel needs an MI355X (torch.cuda.is_available() is False)")
-        self.state = state
-        self.dev = torch.device(device)
-        s = state
-        if str(s.get("meta/fusion_method", "att")) not in ("att", "max"):
-            raise NotImplementedError(f"deployed path: fusion_method {s['meta/fusion_method']!r} ('att' = AttFusion and 'max' = MaxFusion are built here)")
-        self.fusion = 1 if str(s.get("meta/fusion_method", "att")) == "max" else 0
-        self.nx, self.ny, _ = (int(v) for v in s["meta/grid"])
-        self.hm, self.wm = (float(v) for v in s["meta/HW_metres"])
-        self.ratio = float(s["meta/discrete_ratio"])
-        self.layer_nums = [int(v) for v in s["meta/layer_nums"]]
-        self.strides = [int(v) for v in s["meta/layer_strides"]]
-        self.ups = [int(v) for v in s["meta/upsample_strides"]]
-        self.has_codebook = bool(s["meta/has_codebook"])
-        self.emit_single = bool(s["meta/supervise_single"]) if emit_single_preds is None else bool(emit_single_preds)
-        dev = self.dev
+        lut, lut_bias = self._setup_common(state, device, emit_single_preds)
+        s, dev = state, self.dev
 
         # ---- a1: PFN parameters (host struct, passed by value to the kernel) -- or a13, the SECOND encoder ------------
         self.encoder_kind = str(s["meta/encoder"]) if "meta/encoder" in s else "point_pillar"
@@ -363,25 +424,6 @@ class DeployedModel(nn.Module):
             self.comp.append(_ConvLayer(s, "compressor.decoder.1", [(0, 256, *self.comp[1].out_q)], 1, dev))
             self.comp_channels = narrow                                # what would travel: narrow x H x W bytes per agent
             self.final = self.comp[-1]
-        # ---- a6 / a7: codebook -----------------------------------------------------------------------------
-        if self.has_codebook:
-            # seg_num (m) > 1: the state holds the EXTENDED codebook [m * kc][D] (ptq_state.extended_codebook).  Downstream of the encode
-            # everything counts code PLANES: ``levels`` = residual levels * m (the wire's [levels][agents][H*W] planes and the decode table
-            # [levels][kc][D], which is the per-level table over the extended rows read plane by plane); the encode kernels get the true
-            # level count ``enc_levels`` and ``segs``.
-            self.enc_levels, self.segs = int(s["meta/codebook_levels"]), int(s.get("meta/codebook_segs", 1))
-            self.levels = self.enc_levels * self.segs
-            self.ke = int(s["codebook/0/codebook"].shape[0])
-            self.kc = self.ke // self.segs
-            if self.ke > 512 or self.kc > 256:
-                raise NotImplementedError(f"deployed codebook path: seg_num * dict_size <= 512, dict_size <= 256 (got {self.segs} x {self.kc}): "
-                                          "the encode kernels' tile budget (qv2x_codebook_encode_f32)")
-            lut, lut_bias = decode_tables(s, self.enc_levels)
-            lut = lut.reshape(self.levels, self.kc, lut.shape[-1])
-            self.lut = _dev(lut, dev)
-            self.lut_bias = _dev(lut_bias, dev)
-            self.level_blobs = [self._level_blob(l) for l in range(self.enc_levels)]
-            self.level_ptrs = (C.c_void_p * self.enc_levels)(*[b.data_ptr() for b in self.level_blobs])
         # ---- a11: heads ------------------------------------------------------------------------------------
         self.heads = _Heads(s, "", dev)
         self.heads_single = _Heads(s, "_single", dev) if (self.emit_single and "cls_head_single/w_code" in s) else None
@@ -415,12 +457,55 @@ class DeployedModel(nn.Module):
         # launch-plan switches for the ablation tools (tools/bench_*_abl.py); the defaults are the shipped configuration
         self.use_wide_conv, self.batch_deconvs, self.use_chains = True, True, True
         self.chain_max_agents = 1
+
+    # ------------------------------------------------------------------------------------------------------
+    def _setup_common(self, state: Dict[str, np.ndarray], device, emit_single_preds: Optional[bool]):
+        """What every engine of this network sets up first (the fp32 one too): the library and the device, the state's metadata and --
+        with a codebook -- the decode table and the encode's level blobs.  Returns the decode table on the host, ``(lut [levels][kc][256],
+        lut_bias [256])``, or ``(None, None)``."""
+        self.lib = L.load()                      # raises if libqv2x.so is absent: no fallback
+        if not torch.cuda.is_available():
+            raise L.Qv2xError(f"{type(self).__name__} needs an MI355X (torch.cuda.is_available() is False)")
+        self.state, self.dev = state, torch.device(device)
+        s, dev = state, self.dev
+        if str(s.get("meta/fusion_method", "att")) not in ("att", "max"):
+            raise NotImplementedError(f"deployed path: fusion_method {s['meta/fusion_method']!r} ('att' = AttFusion and 'max' = MaxFusion are built here)")
+        self.fusion = 1 if str(s.get("meta/fusion_method", "att")) == "max" else 0
+        self.nx, self.ny, _ = (int(v) for v in s["meta/grid"])
+        self.hm, self.wm = (float(v) for v in s["meta/HW_metres"])
+        self.ratio = float(s["meta/discrete_ratio"])
+        self.layer_nums = [int(v) for v in s["meta/layer_nums"]]
+        self.strides = [int(v) for v in s["meta/layer_strides"]]
+        self.ups = [int(v) for v in s["meta/upsample_strides"]]
+        self.has_codebook = bool(s["meta/has_codebook"])
+        self.emit_single = bool(s["meta/supervise_single"]) if emit_single_preds is None else bool(emit_single_preds)
+        # ---- a6 / a7: codebook -----------------------------------------------------------------------------
+        lut = lut_bias = None
+        if self.has_codebook:
+            # seg_num (m) > 1: the state holds the EXTENDED codebook [m * kc][D] (ptq_state.extended_codebook).  Downstream of the encode
+            # everything counts code PLANES: ``levels`` = residual levels * m (the wire's [levels][agents][H*W] planes and the decode table
+            # [levels][kc][D], which is the per-level table over the extended rows read plane by plane); the encode kernels get the true
+            # level count ``enc_levels`` and ``segs``.
+            self.enc_levels, self.segs = int(s["meta/codebook_levels"]), int(s.get("meta/codebook_segs", 1))
+            self.levels = self.enc_levels * self.segs
+            self.ke = int(s["codebook/0/codebook"].shape[0])
+            self.kc = self.ke // self.segs
+            if self.ke > 512 or self.kc > 256:
+                raise NotImplementedError(f"deployed codebook path: seg_num * dict_size <= 512, dict_size <= 256 (got {self.segs} x {self.kc}): "
+                                          "the encode kernels' tile budget (qv2x_codebook_encode_f32)")
+            lut, lut_bias = decode_tables(s, self.enc_levels)
+            lut = lut.reshape(self.levels, self.kc, lut.shape[-1])
+            self.lut = _dev(lut, dev)
+            self.lut_bias = _dev(lut_bias, dev)
+            self.level_blobs = [self._level_blob(l) for l in range(self.enc_levels)]
+            self.level_ptrs = (C.c_void_p * self.enc_levels)(*[b.data_ptr() for b in self.level_blobs])
         # "exact": every cell through the reference's eleven chained GEMMs.  "two_stage" (round 6, the default wherever its contract holds):
         # the SAME indices by construction -- exact integer candidates, the chain only for the cells a proven bound cannot decide
-        # (encode_two_stage.py).  "collapsed": opt-in and approximate, see collapse_encoder.
-        self._collapsed, self._two_stage = None, None
+        # (encode_two_stage.py; its operands are built with the first workspace).  "collapsed": opt-in and approximate, see collapse_encoder.
+        self._collapsed, self._two_stage, self.two_stage_refused = None, None, None
         self.encode_form = "auto"                                      # "wave": force the wave-per-32-cells encode kernel on every cell (same codes)
         self.encode_mode = "two_stage" if self.two_stage_supported() else "exact"
+        return lut, lut_bias
 
     # ------------------------------------------------------------------------------------------------------
     def _level_blob(self, l: int) -> torch.Tensor:
@@ -491,6 +576,11 @@ class DeployedModel(nn.Module):
         hw = self.fh * self.fw
         if self.has_codebook:
             b["codes"] = torch.empty((self.levels, n, hw), dtype=torch.uint8, device=self.dev)
+        if self.two_stage_supported():
+            if self._two_stage is None and self.encode_mode == "two_stage":
+                self._build_two_stage()                                 # (a6's operands exist before a6 first runs)
+            b["enc_list"] = torch.zeros(3 * n * hw, dtype=torch.int32, device=self.dev)     # three lists (by first undecided level)
+            b["enc_counters"] = torch.zeros(4, dtype=torch.int32, device=self.dev)
         if not self.has_codebook or self.heads_single is not None:
             b["feats"] = torch.empty((n, hw, 256), dtype=torch.float32, device=self.dev)
         self._bufs[n] = b
@@ -680,17 +770,23 @@ class DeployedModel(nn.Module):
         d = L.EncodeDesc()
         d.n, d.h, d.w, d.levels, d.kc, d.segs = n_agents, self.fh, self.fw, self.enc_levels, self.kc, self.segs
         d.in_zx, d.in_delta = int(self.shrink1.out_q[1]), float(self.shrink1.out_q[0])
+        two_stage = self.encode_mode == "two_stage" and self.encode_form == "auto"
+        if two_stage and self._two_stage is None:                      # (switched on after the first workspace; may refuse -> "exact")
+            self._refuse_during_capture("encode_mode 'two_stage'")
+            self._build_two_stage()
+            two_stage = self.encode_mode == "two_stage"
         if self.encode_mode == "collapsed":                           # opt-in: one GEMM + argmin chain, indices may differ at near-ties
             if self.segs != 1 or self.kc > 128:
                 raise NotImplementedError("encode_mode 'collapsed': seg_num 1 and dict_size <= 128 (the exact encode takes the rest)")
             if self._collapsed is None:
+                self._refuse_during_capture("encode_mode 'collapsed'")
                 self._collapsed = tuple(_dev(t, self.dev) for t in collapse_encoder(self.state, self.enc_levels, d.in_delta, d.in_zx))
             gp, bias, tab = self._collapsed
             L.check(self.lib.qv2x_codebook_encode_collapsed_f32(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), L.ptr(codes),
                                                                 L.current_stream()), "qv2x_codebook_encode_collapsed_f32")
             return codes
-        if self.encode_mode == "two_stage" and self.encode_form == "auto":   # exact by construction: candidates on the integer grid + the chain on the undecided
-            return self._encode_two_stage(d, b, codes, n_agents)
+        if two_stage:                                                  # exact by construction: candidates on the integer grid + the chain on the undecided
+            return self._encode_two_stage(d, b, codes)
         if self.encode_mode not in ("exact", "two_stage"):
             raise ValueError(f"encode_mode {self.encode_mode!r}: 'exact' (every cell through the reference's op order), 'two_stage' (the same "
                              "indices: exact integer candidates, the chain only where the bound cannot decide) or 'collapsed' (opt-in, approximate)")
@@ -703,31 +799,36 @@ class DeployedModel(nn.Module):
         return codes
 
     def two_stage_supported(self) -> bool:
-        """seg_num 1, dict_size 32 | 64 | 96 | 128, up to three levels, i8 rows (qv2x_codebook_encode_candidates_i8's contract)"""
-        return bool(self.has_codebook and self.segs == 1 and self.kc <= 128 and self.kc % 32 == 0 and self.enc_levels <= 3
-                    and getattr(self, "encode_rows_i8", True))
+        """seg_num 1, dict_size 32 | 64 | 96 | 128, up to three levels (qv2x_codebook_encode_candidates_i8's contract on i8 rows)"""
+        return bool(self.has_codebook and self.segs == 1 and self.kc <= 128 and self.kc % 32 == 0 and self.enc_levels <= 3)
 
-    def _encode_two_stage(self, d, b, codes, n_agents: int):
-        """a6 as two launches (encode_two_stage.py): qv2x_codebook_encode_candidates_i8 decides every cell it can PROVE, the listed rest
-        goes through the reference-order kernel (qv2x_codebook_encode_listed_f32) -- identical indices, ~a tenth of the fp32 work."""
+    def _refuse_during_capture(self, what: str):
+        if torch.cuda.is_current_stream_capturing():
+            raise L.Qv2xError(f"{what}: its operands are built on the host and uploaded -- not inside a HIP-graph capture; encode once "
+                              "in this mode before capturing")
+
+    def _build_two_stage(self):
+        """The operands of the two-stage encode (encode_two_stage.py) as ``self._two_stage = (gpack, bias, tables, tau, t)``.  A codebook
+        outside the candidate stage's fixed-point contract (or a failed upload) leaves ``encode_mode = "exact"`` -- every cell through the
+        chain, the same indices -- and says why in ``two_stage_refused``."""
         if not self.two_stage_supported():
             raise NotImplementedError("encode_mode 'two_stage': seg_num 1, dict_size <= 128, up to three levels (encode_mode 'exact' takes the rest)")
-        if self._two_stage is None:
-            from .encode_two_stage import candidate_tables
-            try:
-                t = candidate_tables(self.state, self.enc_levels, d.in_delta, d.in_zx)
-            except ValueError as e:                                    # a codebook outside the candidate stage's fixed-point contract:
-                self.encode_mode, self.two_stage_refused = "exact", str(e)   # every cell through the chain (same indices), and say why
-                return self.encode_codes(n_agents, out=codes)
+        from .encode_two_stage import candidate_tables
+        try:
+            t = candidate_tables(self.state, self.enc_levels, float(self.shrink1.out_q[0]), int(self.shrink1.out_q[1]))
             k = np.arange(t["bias"].shape[0], dtype=np.int64) % self.kc
             packed = (128 * t["bias"] + k).astype(np.float64)
-            assert np.array_equal(packed.astype(np.int64), 128 * t["bias"] + k)          # below 2^53: exact
+            if not np.array_equal(packed.astype(np.int64), 128 * t["bias"] + k):
+                raise ValueError("two-stage encode: packed scores not exact in float64")                  # (below 2^53 by construction)
             self._two_stage = (_dev(t["gpack"], self.dev), _dev(packed, self.dev), _dev(t["tables"], self.dev),
                                (C.c_float * (3 * self.enc_levels))(*[float(v) for v in t["tau"].reshape(-1)]), t)
+        except (ValueError, RuntimeError) as e:
+            self.encode_mode, self.two_stage_refused = "exact", str(e)
+
+    def _encode_two_stage(self, d, b, codes):
+        """a6 as two launches (encode_two_stage.py): qv2x_codebook_encode_candidates_i8 decides every cell it can PROVE, the listed rest
+        goes through the reference-order kernel (qv2x_codebook_encode_listed_f32) -- identical indices, ~a tenth of the fp32 work."""
         gp, bias, tab, tau, _ = self._two_stage
-        if "enc_list" not in b:
-            b["enc_list"] = torch.zeros(3 * n_agents * self.fh * self.fw, dtype=torch.int32, device=self.dev)     # three lists (by first undecided level)
-            b["enc_counters"] = torch.zeros(4, dtype=torch.int32, device=self.dev)
         L.check(self.lib.qv2x_codebook_encode_candidates_i8(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
                                                             L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()),
                 "qv2x_codebook_encode_candidates_i8")
@@ -737,7 +838,10 @@ class DeployedModel(nn.Module):
 
     def encode_refine_stats(self, n_agents: int) -> dict:
         """after a two-stage encode of ``n_agents`` frames: how many cells stage 2 recomputed (counters the candidate stage left on the device)"""
-        c = self._workspace(n_agents)["enc_counters"].cpu().numpy().astype(np.int64)
+        if not (self.encode_mode == "two_stage" and self.encode_form == "auto") or "enc_counters" not in self._bufs.get(n_agents, {}):
+            raise L.Qv2xError(f"encode_refine_stats({n_agents}): no two-stage encode of {n_agents} frames here (encode_mode "
+                              f"{self.encode_mode!r}, encode_form {self.encode_form!r}, workspaces {sorted(self._bufs)})")
+        c = self._bufs[n_agents]["enc_counters"].cpu().numpy().astype(np.int64)
         cells = n_agents * self.fh * self.fw
         return {"cells": cells, "refined": int(c[0]), "refined_fraction": float(c[0]) / cells, "first_flagged_at_level": [int(v) for v in c[1:1 + self.enc_levels]]}
 
@@ -774,31 +878,12 @@ class DeployedModel(nn.Module):
         """a7-a11 for ``frames`` scenes whose agents' code planes lie ``agent_stride`` bytes apart in ``gathered`` (frame f at
         ``+ f * frame_stride``); ``pairwise`` f64 [frames, L, L, 4, 4].  With ``own_codes`` (u8 [levels, frames, H*W]) the
         ``*_single`` heads of this rank's own agent run in the same launch as the heads on the fused maps."""
-        hw = self.fh * self.fw
-        sp = None
-        if n_agents == 1 and self.table_heads is not None and self.single_agent_tables and own_codes is not None and frame_stride == hw:
-            # a world of one agent: the own code planes ARE the scene (pairwise here comes from qv2x_pairwise_from_poses_*: T[0][0] of a
-            # world of one is the identity by construction, so the shortcut's contract holds without a read-back)
-            return self._table_heads_out(own_codes, frames)
-        if frames * hw // 32 >= self.fuse_heads_min_tiles and n_agents <= self._one_launch_agents():    # one launch, no fused map in HBM (see finish)
-            preds = self.fuse_heads_scenes(L.ptr(gathered), agent_stride, level_stride, None, pairwise, [f * frame_stride for f in range(frames)],
-                                           [n_agents] * frames, ego)
-            if self.heads_single is not None and own_codes is not None:
-                sp = self._decode_heads_single(own_codes, frames)
-        else:
-            fused = torch.empty((frames, hw, 256), dtype=torch.float32, device=self.dev)
-            self.fuse_scenes(L.ptr(gathered), agent_stride, level_stride, None, pairwise, [f * frame_stride for f in range(frames)],
-                             [n_agents] * frames, fused, ego)
-            if self.heads_single is not None and own_codes is not None:
-                preds, sp = self._heads_pair(fused, frames, own_codes, frames)
-            else:
-                preds = self._run_heads(self.heads, fused, frames, hw)
-        c, r, _ = self.heads.splits
-        out = {"cls_preds": preds[:, :c], "reg_preds": preds[:, c:c + r], "dir_preds": preds[:, c + r:], "preds_tensor": preds}
-        if sp is not None:
-            c, r, _ = self.heads_single.splits
-            out.update({"cls_preds_single": sp[:, :c], "reg_preds_single": sp[:, c:c + r], "dir_preds_single": sp[:, c + r:]})
-        return out
+        # a world of one agent: the own code planes ARE the scene (pairwise here comes from qv2x_pairwise_from_poses_*: T[0][0] of a world of
+        # one is the identity by construction, so the table look-up's contract holds without a read-back)
+        lens = [n_agents] * frames
+        form = self._post_form(lens, None, own_codes is not None and frame_stride == self.fh * self.fw)
+        return self._post(form, L.ptr(gathered), agent_stride, level_stride, None, pairwise, [f * frame_stride for f in range(frames)], lens, ego,
+                          own_codes, frames)
 
     def encode_agents(self, inputs: dict, n_agents: int, taps: Optional[dict] = None):
         """a1-a6 for ``n_agents`` agents.  Returns codes u8 [levels, n, H*W] (or the i8 shrinker output without a codebook)."""
@@ -896,11 +981,9 @@ class DeployedModel(nn.Module):
         sp = torch.empty((n, c1, self.fh, self.fw), dtype=torch.float32, device=self.dev) if c1 else None
         L.check(self.lib.qv2x_table_heads_f32(L.ptr(codes), n * hw, hw, self.levels, self.kc, c0, c1, L.ptr(tab), L.ptr(tb), L.ptr(da), L.ptr(za),
                                               L.ptr(preds), L.ptr(sp) if sp is not None else None, L.current_stream()), "qv2x_table_heads_f32")
-        c, r, _ = self.heads.splits
-        out = {"cls_preds": preds[:, :c], "reg_preds": preds[:, c:c + r], "dir_preds": preds[:, c + r:], "preds_tensor": preds}
+        out = split_heads(preds, self.heads.splits)
         if sp is not None:
-            c, r, _ = self.heads_single.splits
-            out.update({"cls_preds_single": sp[:, :c], "reg_preds_single": sp[:, c:c + r], "dir_preds_single": sp[:, c + r:]})
+            out.update(split_heads(sp, self.heads_single.splits, "_single"))
         return out
 
     def fuse_heads_scenes(self, codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, counts, ego=0, fused_tap=None):
@@ -922,27 +1005,62 @@ class DeployedModel(nn.Module):
                     "qv2x_fuse_heads_batch_f32")
         return out
 
+    def _post_form(self, lens: List[int], taps: Optional[dict], identity) -> str:
+        """How a7-a11 run on scenes of ``lens`` agents: "tables" -- every scene one agent, all heads by table look-up on its code planes, only
+        where the contract ``pairwise[b, 0, 0] = I`` holds (``identity``: a bool, or a callable asked last that may read the matrix back);
+        "one_launch" -- qv2x_fuse_heads_batch_f32, no fused map in HBM; or "fused" -- the fused map, then the heads (what ``taps`` need)."""
+        if (taps is None and self.table_heads is not None and self.single_agent_tables and all(n == 1 for n in lens)
+                and (identity() if callable(identity) else identity)):
+            return "tables"
+        if taps is None and len(lens) * self.fh * self.fw // 32 >= self.fuse_heads_min_tiles and max(lens) <= self._one_launch_agents():
+            return "one_launch"
+        return "fused"
+
+    def _post(self, form: str, codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, lens: List[int], ego: int,
+              own: Optional[torch.Tensor], n_own: int, taps: Optional[dict] = None) -> dict:
+        """a7-a11 in ``form`` (``_post_form``) on the scenes ``lens`` -- the agents' code planes at ``codes_ptr`` (``offsets`` in bytes) or
+        their fp32 shared features ``feats`` (``offsets`` in floats), ``pairwise`` f64 [scenes, L, L, 4, 4] -- and the ``*_single`` heads on
+        ``own``, the code planes u8 [levels, n_own * H*W] of the agents that want them (the scenes themselves in the table form; without a
+        codebook the ``*_single`` heads run on ``feats``).  Returns the model's output dict."""
+        if form == "tables":
+            return self._table_heads_out(own, len(lens))
+        hw, nb = self.fh * self.fw, len(lens)
+        single = self.heads_single is not None and own is not None
+        sp = None
+        if form == "one_launch":                                         # decode + warp + fusion + heads, tile by tile: no fused map in HBM
+            preds = self.fuse_heads_scenes(codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, lens, ego)
+            if single:
+                sp = self._decode_heads_single(own, n_own)
+        else:                                                            # every scene of the call in one launch, then the heads
+            fused = torch.empty((nb, hw, 256), dtype=torch.float32, device=self.dev)
+            self.fuse_scenes(codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, lens, fused, ego)
+            if single:                                                   # the heads on the fused map + the *_single heads on the own codes
+                preds, sp = self._heads_pair(fused, nb, own, n_own)
+            else:
+                preds = self._run_heads(self.heads, fused, nb, hw)
+            if taps is not None:
+                taps["fused"] = fused
+        if self.heads_single is not None and sp is None and feats is not None:
+            sp = self._run_heads(self.heads_single, feats, sum(lens), hw)
+        out = split_heads(preds, self.heads.splits)
+        if sp is not None:
+            out.update(split_heads(sp, self.heads_single.splits, "_single"))
+        return out
+
     def fuse_and_heads(self, codes, agent_stride, level_stride, pairwise_b, n_agents, ego=0) -> dict:
         """a7-a11 on an (all-gathered) code tensor for one scene; ``pairwise_b`` f64 [L, L, 4, 4] on the device."""
-        hw = self.fh * self.fw
-        if pairwise_b.dtype != torch.float64 or not pairwise_b.is_contiguous():
-            pairwise_b = pairwise_b.to(torch.float64).contiguous()
-        fused = torch.empty((1, hw, 256), dtype=torch.float32, device=self.dev)
-        self.fuse(L.ptr(codes), agent_stride, level_stride, None, pairwise_b, n_agents, fused[0], ego)
-        preds = self._run_heads(self.heads, fused, 1, hw)
-        c, r, _ = self.heads.splits
-        return {"cls_preds": preds[:, :c], "reg_preds": preds[:, c:c + r], "dir_preds": preds[:, c + r:], "preds_tensor": preds}
+        return self.fuse_heads_and_single(codes, agent_stride, level_stride, pairwise_b, n_agents, ego, None, 0)
 
     def _decode_heads_single(self, codes, n_agents: int):
         hw = self.fh * self.fw
         hd = self.heads_single
         sp = torch.empty((n_agents, hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
-        if getattr(self, "single_by_tables", False):          # (engines that build their own heads -- the fp32 one -- keep the GEMM form)
+        if self.single_by_tables:
             tab, tb = hd.lut_tables
             L.check(self.lib.qv2x_single_heads_lut_f32(L.ptr(codes), n_agents * hw, hw, self.levels, self.kc, hd.cout, L.ptr(tab), L.ptr(tb),
                                                        L.ptr(hd.da), L.ptr(hd.za), L.ptr(sp), L.current_stream()), "qv2x_single_heads_lut_f32")
             return sp
-        if getattr(self, "single_by_global_tables", False):
+        if self.single_by_global_tables:
             tab, tb = hd.lut_tables
             L.check(self.lib.qv2x_table_heads_f32(L.ptr(codes), n_agents * hw, hw, self.levels, self.kc, hd.cout, 0, L.ptr(tab), L.ptr(tb),
                                                   L.ptr(hd.da), L.ptr(hd.za), L.ptr(sp), None, L.current_stream()), "qv2x_table_heads_f32")
@@ -956,7 +1074,7 @@ class DeployedModel(nn.Module):
         """heads on the fused rows [nb*hw, 256] + *_single heads on the agents' own codes [levels, n_agents*hw]"""
         hw = self.fh * self.fw
         hd, hs = self.heads, self.heads_single
-        if getattr(self, "single_by_tables", False) or getattr(self, "single_by_global_tables", False):   # the single heads are a table look-up: their own launch
+        if self.single_by_tables or self.single_by_global_tables:        # the single heads are a table look-up: their own launch
             return self._run_heads(hd, fused, nb, hw), self._decode_heads_single(codes, n_agents)
         preds = torch.empty((nb, hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
         sp = torch.empty((n_agents, hs.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
@@ -969,29 +1087,14 @@ class DeployedModel(nn.Module):
     def fuse_heads_and_single(self, codes, agent_stride, level_stride, pairwise_b, n_agents, ego, own_codes, n_own: int = 1) -> dict:
         """``fuse_and_heads`` on the gathered codes plus ``single_preds`` on this rank's own codes, the two head passes in one
         launch (what one rank of the multi-GPU driver does after the all-gather)."""
-        if self.heads_single is None or not self.has_codebook:
-            out = self.fuse_and_heads(codes, agent_stride, level_stride, pairwise_b, n_agents, ego)
-            out.update(self.single_preds(own_codes, n_own))
-            return out
-        hw = self.fh * self.fw
-        if pairwise_b.dtype != torch.float64 or not pairwise_b.is_contiguous():
-            pairwise_b = pairwise_b.to(torch.float64).contiguous()
-        fused = torch.empty((1, hw, 256), dtype=torch.float32, device=self.dev)
-        self.fuse(L.ptr(codes), agent_stride, level_stride, None, pairwise_b, n_agents, fused[0], ego)
-        preds, sp = self._heads_pair(fused, 1, own_codes, n_own)
-        c, r, _ = self.heads.splits
-        out = {"cls_preds": preds[:, :c], "reg_preds": preds[:, c:c + r], "dir_preds": preds[:, c + r:], "preds_tensor": preds}
-        c, r, _ = self.heads_single.splits
-        out.update({"cls_preds_single": sp[:, :c], "reg_preds_single": sp[:, c:c + r], "dir_preds_single": sp[:, c + r:]})
-        return out
+        pairwise = pairwise_b.to(torch.float64).contiguous()[None]      # (one scene of the batched fuse: the same device code, qv2x.h)
+        return self._post("fused", L.ptr(codes), agent_stride, level_stride, None, pairwise, [0], [n_agents], ego, own_codes, n_own)
 
     def single_preds(self, codes, n_agents: int) -> dict:
         """``*_preds_single`` (heter_model_baseline.py:224-230): the per-agent heads on each agent's own decoded feature."""
         if self.heads_single is None:
             return {}
-        sp = self._decode_heads_single(codes, n_agents)
-        c, r, _ = self.heads_single.splits
-        return {"cls_preds_single": sp[:, :c], "reg_preds_single": sp[:, c:c + r], "dir_preds_single": sp[:, c + r:]}
+        return split_heads(self._decode_heads_single(codes, n_agents), self.heads_single.splits, "_single")
 
     def _shared_features(self, shrinker_out, n_total: int):
         """no codebook: the fp32 shared feature [n, H*W, 256] is the dequantized shrinker output"""
@@ -1015,90 +1118,36 @@ class DeployedModel(nn.Module):
     def finish(self, enc, n_total: int, data_dict: dict, taps: Optional[dict] = None) -> dict:
         """a7-a11 on the agents' wire data ``enc`` (code planes u8 [levels, n_total * H*W] in agent order, or the i8 shrinker output of a
         model without a codebook): decode + warp + fusion per scene, the heads, the ``*_single`` heads."""
-        pairwise = data_dict["pairwise_t_matrix"]
-        if pairwise.dtype != torch.float64 or not pairwise.is_contiguous():
-            pairwise = pairwise.to(torch.float64).contiguous()
-        nb = pairwise.shape[0]
-        if nb == 1:
-            lens = [n_total]
-        else:
-            rl = data_dict["record_len"]
-            if isinstance(rl, torch.Tensor) and rl.is_cuda and torch.cuda.is_current_stream_capturing():
-                raise ValueError("record_len on the GPU cannot be read during HIP-graph capture: pass a CPU tensor")
-            lens = [int(v) for v in (rl.tolist() if isinstance(rl, torch.Tensor) else rl)]
+        pairwise, lens = scene_layout(data_dict, n_total)
         hw = self.fh * self.fw
         # (no workspace of n_total agents here: a codebook model's post stage only needs the code planes it is handed -- the ego engine of a
         #  heterogeneous scene never encodes n_total agents itself)
         feats = None if self.has_codebook else self._shared_features(enc, n_total)
-        starts = [sum(lens[:bi]) for bi in range(nb)]
-        if (taps is None and self.table_heads is not None and self.single_agent_tables and all(n == 1 for n in lens)
-                and self._self_transforms_are_identity(data_dict["pairwise_t_matrix"])):      # (the caller's own tensor object: see there)
-            return self._table_heads_out(enc, nb)                         # every scene is one agent: all heads straight from its code planes
-        if not pairwise.is_cuda:                                         # a host tensor (the reference's collate output before to_device): copied here
+        form = self._post_form(lens, taps, lambda: self._self_transforms_are_identity(data_dict["pairwise_t_matrix"]))   # (the caller's own tensor object: see there)
+        if form != "tables" and not pairwise.is_cuda:                   # a host tensor (the reference's collate output before to_device): copied here
             if torch.cuda.is_current_stream_capturing():
                 raise ValueError("pairwise_t_matrix on the host cannot be uploaded during HIP-graph capture: pass a device tensor")
             pairwise = pairwise.to(self.dev)
-        one_launch = taps is None and nb * hw // 32 >= self.fuse_heads_min_tiles and max(lens) <= self._one_launch_agents()
-        fused = None if one_launch else torch.empty((nb, hw, 256), dtype=torch.float32, device=self.dev)
-        if one_launch:                                                   # decode + warp + fusion + heads, tile by tile: no fused map in HBM
-            if self.has_codebook:
-                preds = self.fuse_heads_scenes(L.ptr(enc), hw, n_total * hw, None, pairwise, [st * hw for st in starts], lens)
-            else:
-                preds = self.fuse_heads_scenes(None, 0, 0, feats, pairwise, [st * hw * 256 for st in starts], lens)
-        elif self.has_codebook:                                          # every scene of the call in one launch
-            self.fuse_scenes(L.ptr(enc), hw, n_total * hw, None, pairwise, [st * hw for st in starts], lens, fused)
+        starts = [sum(lens[:bi]) for bi in range(len(lens))]
+        if self.has_codebook:
+            out = self._post(form, L.ptr(enc), hw, n_total * hw, None, pairwise, [st * hw for st in starts], lens, 0, enc, n_total, taps)
         else:
-            self.fuse_scenes(None, 0, 0, feats, pairwise, [st * hw * 256 for st in starts], lens, fused)
-        sp = None
-        if one_launch:
-            if self.heads_single is not None and self.has_codebook:
-                sp = self._decode_heads_single(enc, n_total)
-        elif self.heads_single is not None and self.has_codebook:
-            # the heads on the fused map and the *_single heads on every agent's own decoded feature: one launch
-            preds, sp = self._heads_pair(fused, nb, enc, n_total)
-        else:
-            preds = self._run_heads(self.heads, fused, nb, hw)
-        c, r, _ = self.heads.splits
-        out = {"cls_preds": preds[:, :c], "reg_preds": preds[:, c:c + r], "dir_preds": preds[:, c + r:], "preds_tensor": preds}
-        if self.heads_single is not None:
-            if sp is None:
-                sp = self._run_heads(self.heads_single, feats, n_total, hw)
-            c, r, _ = self.heads_single.splits
-            out.update({"cls_preds_single": sp[:, :c], "reg_preds_single": sp[:, c:c + r], "dir_preds_single": sp[:, c + r:]})
+            out = self._post(form, None, 0, 0, feats, pairwise, [st * hw * 256 for st in starts], lens, 0, None, n_total, taps)
         if taps is not None:
             taps["codes"] = enc if self.has_codebook else None
-            taps["fused"] = fused
             taps["features"] = feats
         return out
 
     # ---- HIP-graph replay of a fixed-shape frame ---------------------------------------------------------------
     def capture(self, data_dict: dict):
-        """Capture one frame into a HIP graph (torch.cuda.CUDAGraph on ROCm).  The returned callable replays it on
-        the same input tensors (refresh their contents in place between replays) and returns the same output dict.
+        """Capture one frame into a HIP graph (``capture_forward``): the returned callable replays it on the same input tensors.
 
         The graph relies on the resident canvas being clean between calls (``pillars_to_canvas``): every path of this class leaves it
         so; ``pillars_to_canvas(resident=False)`` refuses to run on a workspace that has such graphs.
         The pillar count M = ``voxel_features.shape[0]`` is baked into the graph: keep M fixed across replays and pad
         unused rows with an out-of-range agent index (``voxel_coords[:, 0] = -1``), which ``pfn_scatter_kernel`` drops.
         ``record_len`` (several scenes per call) must be a CPU tensor: its values shape the launch list."""
-        rl = data_dict.get("record_len")
-        if data_dict["pairwise_t_matrix"].shape[0] > 1 and isinstance(rl, torch.Tensor) and rl.is_cuda:
-            data_dict = dict(data_dict, record_len=rl.cpu())
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self.forward(data_dict)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self.forward(data_dict)
-
-        def replay():
-            graph.replay()
-            return out
-        replay.graph = graph
-        return replay
+        return capture_forward(self, data_dict)
 
 
 class DeployedHeterModel(nn.Module):
@@ -1126,49 +1175,13 @@ class DeployedHeterModel(nn.Module):
     @torch.no_grad()
     def forward(self, data_dict: dict, taps: Optional[dict] = None) -> dict:
         agents = list(data_dict["agent_modality_list"])
-        n_total, hw, lv = len(agents), self.main.fh * self.main.fw, self.main.levels
-        unknown = sorted(set(agents) - set(self.engines))
-        if unknown:
-            raise NotImplementedError(f"deployed heterogeneous path: no engine for modality {unknown}")
-        slots = self._slots.get(tuple(agents))
-        if slots is None:                                              # (built once per layout, outside any HIP-graph capture: capture() warms up first)
-            if torch.cuda.is_current_stream_capturing():
-                raise L.Qv2xError(f"DeployedHeterModel: agent layout {agents} is new and the stream is capturing -- its slot indices are an H2D copy; "
-                                  "run one eager forward of this layout first (DeployedHeterModel.capture does)")
-            slots = {m: torch.as_tensor([i for i, a in enumerate(agents) if a == m], dtype=torch.int64, device=self.dev) for m in self.engines}
-            self._slots[tuple(agents)] = slots
-        enc = torch.empty((lv, n_total * hw), dtype=torch.uint8, device=self.dev)
-        for m, eng in self.engines.items():
-            k = int(slots[m].numel())
-            if not k:
-                continue
-            mt = {} if taps is not None else None
-            codes = eng.encode_agents(data_dict["inputs_" + m], k, mt).view(lv, k, hw)
-            enc.view(lv, n_total, hw).index_copy_(1, slots[m], codes)                                # agent order (a copy, no arithmetic)
-            if taps is not None:
-                taps["modality/" + m] = mt
-        return self.main.finish(enc, n_total, data_dict, taps)
+        enc = assemble_heter_codes("DeployedHeterModel", self.engines, self._slots, agents, data_dict,
+                                   lambda eng, inputs, k, mt: eng.encode_agents(inputs, k, mt), taps)
+        return self.main.finish(enc, len(agents), data_dict, taps)
 
     def capture(self, data_dict: dict):
         """One heterogeneous frame as a HIP graph (see ``DeployedModel.capture``: fixed pillar counts, resident canvases, CPU ``record_len``)."""
-        rl = data_dict.get("record_len")
-        if data_dict["pairwise_t_matrix"].shape[0] > 1 and isinstance(rl, torch.Tensor) and rl.is_cuda:
-            data_dict = dict(data_dict, record_len=rl.cpu())
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self.forward(data_dict)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self.forward(data_dict)
-
-        def replay():
-            graph.replay()
-            return out
-        replay.graph = graph
-        return replay
+        return capture_forward(self, data_dict)
 
 
 def deploy_heter(qt_model, device="cuda", **kw) -> DeployedHeterModel:

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .engine import DeployedModel, _dev, _pack_k4p, decode_tables
+from .engine import DeployedModel, _dev, _pack_k4p
 from .ptq_state import _np, _HEADS, extended_codebook
 
 
@@ -148,24 +148,13 @@ class _F32Heads:
 class DeployedFp32Model(DeployedModel):
     """Same call contract and the same tail (decode + warp + attention, heads, HIP-graph capture, multi-GPU stage interface) as
     ``DeployedModel``; a1-a6 in fp32."""
+    single_by_tables = single_by_global_tables = False                  # (its own heads: the *_single heads keep the GEMM forms)
 
     def __init__(self, state: Dict[str, np.ndarray], device="cuda", emit_single_preds: Optional[bool] = None):
         nn.Module.__init__(self)
-        self.lib = L.load()
-        if not torch.cuda.is_available():
-            raise L.Qv2xError("DeployedFp32Model needs an MI355X (torch.cuda.is_available() is False)")
-        self.state, self.dev = state, torch.device(device)
+        self._setup_common(state, device, emit_single_preds)           # metadata, decode table, level blobs (engine.py)
         s, dev = state, self.dev
-        self.nx, self.ny, _ = (int(v) for v in s["meta/grid"])
-        self.hm, self.wm = (float(v) for v in s["meta/HW_metres"])
-        self.ratio = float(s["meta/discrete_ratio"])
-        self.layer_nums = [int(v) for v in s["meta/layer_nums"]]
-        self.strides = [int(v) for v in s["meta/layer_strides"]]
-        self.ups = [int(v) for v in s["meta/upsample_strides"]]
-        self.has_codebook = bool(s["meta/has_codebook"])
         self.compress = False
-        self.fusion = 1 if str(s.get("meta/fusion_method", "att")) == "max" else 0
-        self.emit_single = bool(s["meta/supervise_single"]) if emit_single_preds is None else bool(emit_single_preds)
         f32a = lambda a: (C.c_float * len(a))(*[float(np.float32(v)) for v in a])
         self.pfn_w, self.pfn_b = f32a(s["pfn/w"].reshape(-1)), f32a(s["pfn/bias"])
         self.pfn_vox, self.pfn_off = f32a(s["meta/voxel"]), f32a(s["meta/offset"])
@@ -180,21 +169,15 @@ class DeployedFp32Model(DeployedModel):
         self.shrink1 = _F32Conv(s, "shrinker_m1.layers.0.double_conv.1", 1, dev)
         if self.shrink1.cout != 256:
             raise NotImplementedError("deployed path expects a 256-channel shared feature")
-        if self.has_codebook:
-            self.enc_levels, self.segs = int(s["meta/codebook_levels"]), int(s.get("meta/codebook_segs", 1))
-            self.levels = self.enc_levels * self.segs                  # code planes (engine.py)
-            self.ke = int(s["codebook/0/codebook"].shape[0])
-            self.kc = self.ke // self.segs
-            lut, lut_bias = decode_tables(s, self.enc_levels)
-            lut = lut.reshape(self.levels, self.kc, lut.shape[-1])
-            self.lut, self.lut_bias = _dev(lut, dev), _dev(lut_bias, dev)
-            self.level_blobs = [self._level_blob(l) for l in range(self.enc_levels)]
-            self.level_ptrs = (C.c_void_p * self.enc_levels)(*[b.data_ptr() for b in self.level_blobs])
         self.heads = _F32Heads(s, "", dev)
         self.heads_single = _F32Heads(s, "_single", dev) if (self.emit_single and "cls_head_single/w" in s) else None
         self._bufs: Dict[int, dict] = {}
         self.chains = [None] * len(self.blocks)
         self.use_wide_conv = self.batch_deconvs = self.use_chains = False
+
+    def two_stage_supported(self) -> bool:
+        """never: the two-stage encode's candidate stage reads i8 rows, this model's shrinker writes fp32 ones"""
+        return False
 
     # ---- buffers: fp32 NHWC with a zero border ---------------------------------------------------------------------------
     def _workspace(self, n: int) -> dict:

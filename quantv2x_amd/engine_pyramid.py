@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .engine import _ConvLayer, _DeconvLayer, _Heads, _dev, _pack_k4p, decode_tables, wave_section
+from .engine import (_ConvLayer, _DeconvLayer, _Heads, _dev, _pack_k4p, assemble_heter_codes, capture_forward, decode_tables, scene_layout,
+                     split_heads, wave_section)
 
 
 def _q(state, name):
@@ -605,9 +606,7 @@ class DeployedPyramidModel(nn.Module):
                                         L.ptr(preds), st()), "qv2x_heads_f32")
         if taps is not None:
             taps["cat"], taps[self.shrink0.name], taps[self.shrink1.name], taps["features"] = b["cat"], b["s0"], b["s1"], feats_f32
-        c, r, _ = hd.splits
-        return {"pyramid": "collab", "cls_preds": preds[:, :c], "reg_preds": preds[:, c:c + r], "dir_preds": preds[:, c + r:], "preds_tensor": preds,
-                "occ_single_list": occ_maps}
+        return {"pyramid": "collab", **split_heads(preds, hd.splits), "occ_single_list": occ_maps}
 
     # ---- stage interface of the multi-GPU driver (quantv2x_amd/dist.py): one agent per rank, code planes + pose over the link ----------
     def wire_shape(self):
@@ -630,9 +629,7 @@ class DeployedPyramidModel(nn.Module):
                                      pairwise[f:f + 1], ego) for f in range(frames)]
         if frames == 1:
             return outs[0]
-        preds = torch.cat([o["preds_tensor"] for o in outs])
-        c, r, _ = self.heads.splits
-        return {"pyramid": "collab", "cls_preds": preds[:, :c], "reg_preds": preds[:, c:c + r], "dir_preds": preds[:, c + r:], "preds_tensor": preds,
+        return {"pyramid": "collab", **split_heads(torch.cat([o["preds_tensor"] for o in outs]), self.heads.splits),
                 "occ_single_list": [torch.cat([o["occ_single_list"][l] for o in outs]) for l in range(len(self.occ))]}
 
     # ---- the reference's model contract ------------------------------------------------------------------------------------------------
@@ -642,16 +639,7 @@ class DeployedPyramidModel(nn.Module):
         n_total = len(agents)
         if any(str(a) != "m1" for a in agents):
             raise NotImplementedError("deployed path: every agent is the LiDAR modality 'm1'")
-        pairwise = data_dict["pairwise_t_matrix"]
-        if pairwise.dtype != torch.float64 or not pairwise.is_contiguous():
-            pairwise = pairwise.to(torch.float64).contiguous()
-        if pairwise.shape[0] == 1:
-            lens = [n_total]
-        else:
-            rl = data_dict["record_len"]
-            if isinstance(rl, torch.Tensor) and rl.is_cuda and torch.cuda.is_current_stream_capturing():
-                raise ValueError("record_len on the GPU cannot be read during HIP-graph capture: pass a CPU tensor")
-            lens = [int(v) for v in (rl.tolist() if isinstance(rl, torch.Tensor) else rl)]
+        pairwise, lens = scene_layout(data_dict, n_total)
         if not self.has_codebook:                                    # heter_pyramid_collab_mc: the agents' codes go straight into the pyramid
             canvas = self.pillars_to_canvas(data_dict["inputs_m1"], n_total)
             if taps is not None:
@@ -668,24 +656,25 @@ class DeployedPyramidModel(nn.Module):
 
     def capture(self, data_dict: dict):
         """One frame as a HIP graph (see ``DeployedModel.capture``: fixed pillar count, CPU ``record_len``)."""
-        rl = data_dict.get("record_len")
-        if data_dict["pairwise_t_matrix"].shape[0] > 1 and isinstance(rl, torch.Tensor) and rl.is_cuda:
-            data_dict = dict(data_dict, record_len=rl.cpu())
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self.forward(data_dict)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self.forward(data_dict)
+        return capture_forward(self, data_dict)
 
-        def replay():
-            graph.replay()
-            return out
-        replay.graph = graph
-        return replay
+
+def modality_names_of(agent_modality_list, modality_names: List[str]) -> List[str]:
+    """``agent_modality_list`` as modality names.  The reference's heter_pyramid_collab takes a TENSOR of 1-based modality codes and maps it
+    onto modality_name_list (heter_pyramid_collab.py:143-150; the plugin mirror's _named_modalities does the same); names pass through.
+    A code outside 1..len(modality_names) -- 0 included -- or a bool is refused."""
+    aml = agent_modality_list.tolist() if isinstance(agent_modality_list, torch.Tensor) else list(agent_modality_list)
+    names = []
+    for a in aml:
+        if isinstance(a, (bool, np.bool_)):
+            raise ValueError(f"agent_modality_list: {a!r} is neither a modality name nor a code 1..{len(modality_names)}")
+        if isinstance(a, (int, np.integer)) or (isinstance(a, float) and a == int(a)):
+            if not 1 <= int(a) <= len(modality_names):
+                raise ValueError(f"agent_modality_list: modality code {a} outside 1..{len(modality_names)} ({modality_names})")
+            names.append(modality_names[int(a) - 1])
+        else:
+            names.append(str(a))
+    return names
 
 
 class DeployedHeterPyramidModel(nn.Module):
@@ -713,39 +702,11 @@ class DeployedHeterPyramidModel(nn.Module):
 
     @torch.no_grad()
     def forward(self, data_dict: dict, taps: Optional[dict] = None) -> dict:
-        # the reference's heter_pyramid_collab takes a TENSOR of 1-based modality codes and maps it onto modality_name_list
-        # (heter_pyramid_collab.py:143-150; the plugin mirror's _named_modalities does the same); names pass through
-        aml = data_dict["agent_modality_list"]
-        aml = aml.tolist() if isinstance(aml, torch.Tensor) else list(aml)
-        agents = [self.modality_names[int(a) - 1] if isinstance(a, (int, np.integer)) or (isinstance(a, float) and a == int(a)) else str(a) for a in aml]
+        agents = modality_names_of(data_dict["agent_modality_list"], self.modality_names)
         n_total, hw, lv = len(agents), self.main.fh * self.main.fw, self.main.levels
-        unknown = sorted(set(agents) - set(self.engines))
-        if unknown:
-            raise NotImplementedError(f"deployed heterogeneous Pyramid path: no engine for modality {unknown}")
-        slots = self._slots.get(tuple(agents))
-        if slots is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise L.Qv2xError(f"DeployedHeterPyramidModel: agent layout {agents} is new and the stream is capturing; run one eager forward first")
-            slots = {m: torch.as_tensor([i for i, a in enumerate(agents) if a == m], dtype=torch.int64, device=self.dev) for m in self.engines}
-            self._slots[tuple(agents)] = slots
-        pairwise = data_dict["pairwise_t_matrix"]
-        if pairwise.dtype != torch.float64 or not pairwise.is_contiguous():
-            pairwise = pairwise.to(torch.float64).contiguous()
-        if pairwise.shape[0] == 1:
-            lens = [n_total]
-        else:
-            rl = data_dict["record_len"]
-            lens = [int(v) for v in (rl.tolist() if isinstance(rl, torch.Tensor) else rl)]
-        enc = torch.empty((lv, n_total * hw), dtype=torch.uint8, device=self.dev)
-        for m, eng in self.engines.items():
-            k = int(slots[m].numel())
-            if not k:
-                continue
-            mt = {} if taps is not None else None
-            codes = eng.encode_features(data_dict["inputs_" + m], k, mt).view(lv, k, hw)
-            enc.view(lv, n_total, hw).index_copy_(1, slots[m], codes)          # agent order (a copy, no arithmetic)
-            if taps is not None:
-                taps["modality/" + m] = mt
+        pairwise, lens = scene_layout(data_dict, n_total)
+        enc = assemble_heter_codes("DeployedHeterPyramidModel", self.engines, self._slots, agents, data_dict,
+                                   lambda eng, inputs, k, mt: eng.encode_features(inputs, k, mt), taps)
         if taps is not None:
             taps["codes"] = enc.view(lv, n_total, hw)
         return self.main.decode_features(enc, hw, n_total * hw, lens, pairwise, 0, taps)

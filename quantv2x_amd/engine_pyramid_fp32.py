@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .engine import _dev, decode_tables
+from .engine import _dev, decode_tables, scene_layout, split_heads
 from .engine_fp32 import _F32Heads, _fold, pack_k8
 from .ptq_state import _HEADS, _np, extended_codebook
 
@@ -331,9 +331,7 @@ class DeployedPyramidFp32Model(nn.Module):
                                         L.ptr(hd.da), L.ptr(hd.za), L.ptr(preds), L.current_stream()), "qv2x_heads_f32")
         if taps is not None:
             taps["cat"], taps[self.shrink1.name] = b["cat"], b["s1"]
-        c, r, _ = hd.splits
-        return {"pyramid": "collab", "cls_preds": preds[:, :c], "reg_preds": preds[:, c:c + r], "dir_preds": preds[:, c + r:], "preds_tensor": preds,
-                "occ_single_list": occ_maps}
+        return {"pyramid": "collab", **split_heads(preds, hd.splits), "occ_single_list": occ_maps}
 
     @torch.no_grad()
     def decode_features(self, codes, agent_stride: int, level_stride: int, lens: List[int], pairwise: torch.Tensor, ego: int = 0,
@@ -357,14 +355,7 @@ class DeployedPyramidFp32Model(nn.Module):
         n_total = len(agents)
         if any(str(a) != "m1" for a in agents):
             raise NotImplementedError("deployed path: every agent is the LiDAR modality 'm1'")
-        pairwise = data_dict["pairwise_t_matrix"]
-        if pairwise.dtype != torch.float64 or not pairwise.is_contiguous():
-            pairwise = pairwise.to(torch.float64).contiguous()
-        if pairwise.shape[0] == 1:
-            lens = [n_total]
-        else:
-            rl = data_dict["record_len"]
-            lens = [int(v) for v in (rl.tolist() if isinstance(rl, torch.Tensor) else rl)]
+        pairwise, lens = scene_layout(data_dict, n_total)
         if not self.has_codebook:
             x = self.agent_features(data_dict["inputs_m1"], n_total, len(lens), taps)
             return self._pyramid_and_heads(x, lens, pairwise, 0, taps)

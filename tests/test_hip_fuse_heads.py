@@ -175,3 +175,95 @@ def test_table_heads_at_batch_size_four_cells_per_lane(c0, c1, kc, hw, n):
         for c in range(lo, hi):
             got = o0[:, c] if c < c0 else o1[:, c - c0]
             assert torch.equal(got, want[:, c - lo]), c
+
+
+class _Recorder:
+    """``eng.lib`` stand-in: records the name of every ``qv2x_*`` entry called and forwards the call to the library."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("qv2x_"):
+            return fn
+
+        def call(*args):
+            self.calls.append(name)
+            return fn(*args)
+        return call
+
+
+def _launches(eng, run):
+    rec = _Recorder(eng.lib)
+    eng.lib = rec
+    try:
+        run()
+    finally:
+        eng.lib = rec._lib
+    torch.cuda.synchronize()
+    return [c[len("qv2x_"):] for c in rec.calls]
+
+
+@pytest.fixture(scope="module")
+def post_engines():
+    from quantv2x_amd.engine import deploy
+    from quantv2x_amd.ptq_state import export_ptq_state
+    state = export_ptq_state(calibrated_plugin("tiny", n_agents=2))
+    plain = export_ptq_state(calibrated_plugin("tiny", n_agents=2, codebook=False))
+    return {"single": deploy(state=state), "none": deploy(state=state, emit_single_preds=False), "no_codebook": deploy(state=plain)}
+
+
+# the *_single heads' launch as the engine's flags select it (S) and the heads pair on a fused map (P)
+_SINGLE_FORMS = {"lut": (True, False), "global": (False, True), "gemm": (False, False)}
+
+
+def _s(eng):
+    if eng.single_by_tables:
+        return ["single_heads_lut_f32"]
+    return ["table_heads_f32"] if eng.single_by_global_tables else ["decode_heads_f32"]
+
+
+def _p(eng):
+    return ["heads_f32"] + _s(eng) if (eng.single_by_tables or eng.single_by_global_tables) else ["heads_pair_f32"]
+
+
+@pytest.mark.parametrize("entry", ["finish_tables", "finish_one_launch", "finish_two_launches", "finish_two_launches_no_single", "finish_taps",
+                                   "frames_tables", "frames_one_launch", "frames_two_launches", "fuse_and_heads", "fuse_heads_and_single",
+                                   "finish_no_codebook"])
+def test_post_stage_launch_sequence(post_engines, entry):
+    """a7-a11: which kernels each entry point launches, pinned by name for every form (the table look-up, one launch, the fused map + heads)
+    and every *_single heads form the engine's flags select."""
+    eng = post_engines["none" if entry == "finish_two_launches_no_single" else "no_codebook" if entry == "finish_no_codebook" else "single"]
+    saved = eng.fuse_heads_min_tiles, eng.single_agent_tables, eng.single_by_tables, eng.single_by_global_tables
+    # (the entries of the multi-GPU driver and the parity tests take ONE scene)
+    counts = ([1, 1] if entry in ("finish_tables", "finish_taps") else [2, 1] if entry.startswith("finish") else
+              [1] if entry == "frames_tables" else [2])
+    dd = _batch([scene_np(n, seed=41 + i) for i, n in enumerate(counts)])
+    n = sum(counts)
+    try:
+        forms = _SINGLE_FORMS.items() if eng.heads_single is not None and eng.has_codebook else [("-", saved[2:])]
+        for form, flags in forms:
+            eng.single_by_tables, eng.single_by_global_tables = flags
+            eng.fuse_heads_min_tiles = 0 if entry.endswith("one_launch") or entry == "finish_taps" else 1 << 30
+            enc = eng.encode_agents(dd["inputs_m1"], n).clone()
+            hw = eng.fh * eng.fw
+            pw = dd["pairwise_t_matrix"].to(torch.float64).contiguous()
+            own = enc.view(-1, n, hw)[:, :1].contiguous() if eng.has_codebook else None
+            if entry.startswith("finish"):
+                got = _launches(eng, lambda: eng.finish(enc, n, dd, {} if entry == "finish_taps" else None))
+            elif entry.startswith("frames"):
+                got = _launches(eng, lambda: eng.fuse_frames_and_heads(enc, hw, n * hw, hw, pw, n, 0, own, 1))
+            elif entry == "fuse_and_heads":
+                got = _launches(eng, lambda: eng.fuse_and_heads(enc, hw, n * hw, pw[0], n))
+            else:
+                got = _launches(eng, lambda: eng.fuse_heads_and_single(enc, hw, n * hw, pw[0], n, 0, own))
+            want = {"finish_tables": ["table_heads_f32"], "frames_tables": ["table_heads_f32"],
+                    "finish_one_launch": ["fuse_heads_batch_f32"] + _s(eng), "frames_one_launch": ["fuse_heads_batch_f32"] + _s(eng),
+                    "finish_two_launches": ["fuse_att_batch_f32"] + _p(eng), "frames_two_launches": ["fuse_att_batch_f32"] + _p(eng),
+                    "finish_taps": ["fuse_att_batch_f32"] + _p(eng), "finish_two_launches_no_single": ["fuse_att_batch_f32", "heads_f32"],
+                    "fuse_and_heads": ["fuse_att_batch_f32", "heads_f32"], "fuse_heads_and_single": ["fuse_att_batch_f32"] + _p(eng),
+                    "finish_no_codebook": ["dequant_i8_f32", "fuse_att_batch_f32", "heads_f32", "heads_f32"]}[entry]
+            assert got == want, (form, got)
+    finally:
+        eng.fuse_heads_min_tiles, eng.single_agent_tables, eng.single_by_tables, eng.single_by_global_tables = saved
