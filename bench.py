@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- frames/s of the quantized per-agent encode + intermediate-fusion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--inflight F] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--inflight F] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,7 +9,7 @@ A *step* is one pass of the whole hot path (a1-a11: PFN + scatter, int8 backbone
 decode + warp + attention, heads) over one batch of B synthetic V2X-Real-shaped frames (default B = 32: the reference's
 model contract has a batch dimension, ``record_len`` / ``pairwise_t_matrix[B]``), replayed as HIP graphs; at N = 1, F = 2
 such batches are in flight on two streams (the next batch's PFN / backbone fill the tail of the previous batch's encode).
-``value`` = frames per second over exactly K steps; the p50 latency of ONE frame run alone is reported next to it, and
+``value`` = frames per second over exactly K steps; with ``--full`` the p50 latency of ONE frame run alone is reported next to it, and
 ``value_one_frame_at_a_time`` is its reciprocal throughput (round 1's ``value``).
 
 With N GPUs, rank r owns agent r (one process per GPU): every step each rank encodes B frames of its agent, ONE RCCL
@@ -18,7 +18,10 @@ N-agent frames; ``value`` = N * B * K / (max-over-ranks time).  Per-GPU work is 
 ``--rehearse-world W`` (one GPU): rank 0's step of the W-GPU line with the all-gather replaced by a device copy -- its own line, not a
 multi-GPU measurement.
 
-Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line (contract in the task prompt) with
+Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line: the headline (``value``, ``ms_per_step``) and the
+configuration it ran.  A plain run does nothing else: it sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints.
+``--full`` measures everything beside the headline after the timed steps -- the ego-only figure of an N-GPU run, the one-frame latency,
+the extras (fp32 path, multi-agent, Pyramid, SECOND, other encode modes and codebooks, points -> boxes, rehearsals) and
   roofline         the dominant kernel by time (codebook_encode_wave_kernel: f32 MFMA), launch duration from HIP events
   roofline_stages  every stage of the frame against its own bound (int8 MFMA / f32 MFMA / HBM), same method
   cpu_baseline     the CPU oracle (``oracle/``, the checker -- never the product) on the host cores; and
@@ -1043,9 +1046,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=32, help="frames per step (per rank); 32: every persistent conv workgroup owns several items in a row (DESIGN.md 5)")
     ap.add_argument("--inflight", type=int, default=2, help="batches in flight per rank (streams / engines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra fields (fp32 path, multi-agent, Pyramid, SECOND, collapsed encode, "
-                    "points -> boxes): the line's contract fields, roofline and roofline_stages only (profiling passes)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, measure everything beside the headline: the ego-only figure "
+                    "(N > 1), the one-frame latency, roofline and roofline_stages, the extra fields and the CPU baselines.  Without it the line "
+                    "carries the headline and its configuration only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline, parity and cpu_baseline_torch")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra fields (fp32 path, multi-agent, Pyramid, SECOND, "
+                    "collapsed encode, points -> boxes): the line's contract fields, roofline and roofline_stages only (profiling passes)")
     ap.add_argument("--force-sharded", action="store_true", help="run the N>1 code path (HIP graphs around the collective) with one rank")
     ap.add_argument("--link", default="torch", choices=["torch", "rccl"], help="N>1 collective: torch.distributed or qv2x_allgather_codes")
     ap.add_argument("--graph-link", action="store_true", help="with --link rccl: the all-gather is captured INSIDE the step's one HIP graph "
@@ -1071,6 +1077,8 @@ def main():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and (args.rehearse_world or args.dry_run_ranks):
         ap.error("--dump-outputs writes the outputs of the timed steps of the main line: not with --rehearse-world or --dry-run-ranks")
+    if (args.no_cpu_baseline or args.no_extras) and not args.full:
+        ap.error("--no-cpu-baseline and --no-extras trim the --full line: give --full with them")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_run_ranks):
         # a bare `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU) and relay rank 0's line
@@ -1204,7 +1212,7 @@ def main():
         # before anything else runs on the device: the later measurements reuse engine 0's workspace
         written = dump_outputs(last_out[0], args.dump_outputs)
         print(f"[bench] wrote the last timed step's outputs to {args.dump_outputs}: " + json.dumps(written), file=sys.stderr, flush=True)
-    if sharded_mode and not args.ego_only:
+    if args.full and sharded_mode and not args.ego_only:
         # the parity configuration of SURVEY 8(e)(i) beside the headline: only rank 0 fuses -- its output is the single-process model's
         del shardeds
         step_e, shardeds = make_step(True)
@@ -1214,30 +1222,31 @@ def main():
                     "frames_per_step": B, "note": "ego_only: every rank encodes and joins the all-gather, rank 0 alone runs a7-a11 (the reference's "
                     "single-ego output, SURVEY 8(e)(i)); `value` above counts every rank's own ego view (8(e)(ii))"}
 
-    # p50 latency of ONE frame run alone (device-synchronised), outside the timed region
-    lat = []
-    if not sharded_mode:
-        _, one, _, _ = frame_batch(1, 0, 1, device)
-        solo = eng.capture(one)
-    else:
-        _, _, mine1, _ = frame_batch(world, rank, 1, device, layout=wl["layout"], max_cav=wl["max_cav"], own_only=world > 1)
-        sh1 = AgentShardedModel(eng, frames=1, link=args.link, max_cav=wl["max_cav"], ego_only=args.ego_only, graph_link=args.graph_link)
-        solo = lambda: sh1.forward(mine1, pose)
-    for _ in range(10):
-        solo()
-    for _ in range(50):
+    if args.full:
+        # p50 latency of ONE frame run alone (device-synchronised), outside the timed region
+        lat = []
+        if not sharded_mode:
+            _, one, _, _ = frame_batch(1, 0, 1, device)
+            solo = eng.capture(one)
+        else:
+            _, _, mine1, _ = frame_batch(world, rank, 1, device, layout=wl["layout"], max_cav=wl["max_cav"], own_only=world > 1)
+            sh1 = AgentShardedModel(eng, frames=1, link=args.link, max_cav=wl["max_cav"], ego_only=args.ego_only, graph_link=args.graph_link)
+            solo = lambda: sh1.forward(mine1, pose)
+        for _ in range(10):
+            solo()
+        for _ in range(50):
+            barrier()
+            a = time.perf_counter()
+            solo()
+            torch.cuda.synchronize()
+            lat.append((time.perf_counter() - a) * 1e3)
+        lat.sort()
         barrier()
-        a = time.perf_counter()
-        solo()
-        torch.cuda.synchronize()
-        lat.append((time.perf_counter() - a) * 1e3)
-    lat.sort()
-    barrier()
-    ta = time.perf_counter()
-    for _ in range(50):
-        solo()
-    barrier()
-    one_at_a_time = 50 * (world if (sharded_mode and not args.ego_only) else 1) / (time.perf_counter() - ta)
+        ta = time.perf_counter()
+        for _ in range(50):
+            solo()
+        barrier()
+        one_at_a_time = 50 * (world if (sharded_mode and not args.ego_only) else 1) / (time.perf_counter() - ta)
 
     if rank == 0:
         hw = eng.fh * eng.fw
@@ -1263,13 +1272,14 @@ def main():
                                            if eng.encode_mode == "two_stage" else f"{eng.encode_mode}: every cell through the reference-order fp32 chain"),
                        "wire_bytes_per_agent_frame": 3 * hw,
                        "rccl_world_size": dist.get_world_size() if dist.is_initialized() else 1},
-            "latency_ms_p50": round(lat[len(lat) // 2], 4), "latency_ms_p95": round(lat[int(len(lat) * 0.95) - 1], 4),
-            "latency_note": "one frame run alone (batch 1, nothing else in flight), host-timed around launch + device sync",
-            "value_one_frame_at_a_time": round(one_at_a_time, 2),
         }
+        if args.full:
+            line.update({"latency_ms_p50": round(lat[len(lat) // 2], 4), "latency_ms_p95": round(lat[int(len(lat) * 0.95) - 1], 4),
+                         "latency_note": "one frame run alone (batch 1, nothing else in flight), host-timed around launch + device sync",
+                         "value_one_frame_at_a_time": round(one_at_a_time, 2)})
         if ego_line is not None:
             line["ego_only"] = ego_line
-        if sharded_mode and not args.no_extras:
+        if args.full and sharded_mode and not args.no_extras:
             # north_star: ">= 6x 1 -> 8 at matched detection output".  The matched output is the ego-0 frame of every scene: this job's ego-only
             # figure over the SAME scenes (all `world` agents) on one GPU, measured here on rank 0 while the other ranks wait at the barrier below
             try:
@@ -1281,9 +1291,10 @@ def main():
                                                                  "wholly on one GPU (every agent encoded here, ego = agent 0); both produce the reference's single-ego output"}
             except Exception as e:
                 line["scaling_vs_one_gpu_same_scene"] = {"error": repr(e)[:300]}
-        roof, stages = rooflines(eng, full if not sharded_mode else frame_batch(1, 0, B, device)[1], B, iters=max(10, args.steps // 5))
-        line["roofline"], line["roofline_stages"] = roof, stages
-        if world == 1 and not sharded_mode and not args.no_extras:
+        if args.full:
+            roof, stages = rooflines(eng, full if not sharded_mode else frame_batch(1, 0, B, device)[1], B, iters=max(10, args.steps // 5))
+            line["roofline"], line["roofline_stages"] = roof, stages
+        if args.full and world == 1 and not sharded_mode and not args.no_extras:
             # the same frame on the fp32 HIP path (the un-quantized model, engine_fp32.py): what W8A8 buys on this GPU
             from quantv2x_amd.engine import deploy as _deploy
             e32 = _deploy(fp_model)
@@ -1340,7 +1351,7 @@ def main():
                 line["sharded_world1"] = sharded_world1_line(state, B, device)
             except Exception as e:
                 line["sharded_world1"] = {"error": repr(e)[:300]}
-        if not args.no_cpu_baseline and world == 1 and not sharded_mode:       # reported on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not sharded_mode:       # reported on rank 0 at N = 1 only
             # the CPU checker on frames of THIS batch; each frame it finishes is compared with what the timed graphs computed (both
             # engines' workspaces hold their last replay: same inputs, so the same bytes) -- the parity gate of SURVEY 8(d)
             from quantv2x_amd import synth

@@ -58,7 +58,7 @@ def put(key, match, units, unit, split=None):
         nf = len(sel)
     res[key] = {"kernel": names[0][:120], "grid": g, "launches_averaged": nf, "FETCH_SIZE_KiB": round(f, 1), "WRITE_SIZE_KiB": round(w, 1),
                 "traffic_bytes_per_launch": int((2 * f + w) * 1024), "units_per_launch": units, "unit": unit,
-                "note": "(2 x FETCH_SIZE + WRITE_SIZE) x 1 KiB, two separate --pmc passes of `python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extras`"}
+                "note": "(2 x FETCH_SIZE + WRITE_SIZE) x 1 KiB, two separate --pmc passes of `python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-extras`"}
 
 
 put("deconv", lambda k: "deconv_ps_batch_kernel" in k, frames, "agent-frames")
