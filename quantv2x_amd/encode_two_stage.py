@@ -35,10 +35,13 @@ So ``E_l(N0) = ea_l + eb_l N0 + ec_l N0^2`` bounds ``|(D_hat_l[a] - D_hat_l[b]) 
 counted twice), and with stage 1's own error e2 per score (the grid: ``0.5 sum |code - zx| + 0.5 (1 + tables)`` units) a candidate whose gap
 exceeds ``tau_l = E_l + 2 e2`` is the fp32 chain's strict minimum: ``D_hat[a] - D_hat[b] <= (s~_a - s~_b) + 2 e2 + E_l < 0``.
 Measured on the bench's model: tau = 0.13 / 0.28 / 0.48 at levels 0 / 1 / 2 for a typical cell (|x| = 134), 12 % of the cells go to stage 2
-(the propagated part is ~1000x what the chain really loses -- worst-case rounding -- but the gaps are O(1), so it is affordable).
+(the propagated part is ~1000x what the chain really loses -- worst-case rounding -- but the gaps are O(1), so it is affordable; tau as a
+whole is ~15x the largest gap difference measured).
 
 ``tests/test_encode_two_stage_cpu.py`` pins the theory on the CPU: the numpy emulation of stage 1 (``candidate_emulate``) against the oracle
-on the reference's golden rows and on synthetic ones -- every accepted cell equal at every level, flagged fraction reported."""
+on the reference's golden rows and on synthetic ones -- every accepted cell equal at every level, flagged fraction reported -- and, on the
+hostile models and rows of ``tests/_encode_families.py``, the inequality above on every cell, every score against a float64 chain, and the
+kernel's integer ranges."""
 from typing import Dict
 
 import numpy as np

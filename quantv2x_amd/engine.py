@@ -809,7 +809,7 @@ class DeployedModel(nn.Module):
 
     def _build_two_stage(self):
         """The operands of the two-stage encode (encode_two_stage.py) as ``self._two_stage = (gpack, bias, tables, tau, t)``.  A codebook
-        outside the candidate stage's fixed-point contract (or a failed upload) leaves ``encode_mode = "exact"`` -- every cell through the
+        outside the candidate stage's fixed-point contract (or ANY failure of the host algebra or the upload) leaves ``encode_mode = "exact"`` -- every cell through the
         chain, the same indices -- and says why in ``two_stage_refused``."""
         if not self.two_stage_supported():
             raise NotImplementedError("encode_mode 'two_stage': seg_num 1, dict_size <= 128, up to three levels (encode_mode 'exact' takes the rest)")
@@ -822,8 +822,8 @@ class DeployedModel(nn.Module):
                 raise ValueError("two-stage encode: packed scores not exact in float64")                  # (below 2^53 by construction)
             self._two_stage = (_dev(t["gpack"], self.dev), _dev(packed, self.dev), _dev(t["tables"], self.dev),
                                (C.c_float * (3 * self.enc_levels))(*[float(v) for v in t["tau"].reshape(-1)]), t)
-        except (ValueError, RuntimeError) as e:
-            self.encode_mode, self.two_stage_refused = "exact", str(e)
+        except Exception as e:                                          # whatever the host algebra raises (LinAlgError, FloatingPointError, ...)
+            self.encode_mode, self.two_stage_refused = "exact", str(e) or type(e).__name__
 
     def _encode_two_stage(self, d, b, codes):
         """a6 as two launches (encode_two_stage.py): qv2x_codebook_encode_candidates_i8 decides every cell it can PROVE, the listed rest

@@ -4,7 +4,9 @@ rounding; every accepted cell must then carry the oracle's indices (the referenc
 Checked on the reference's own 35 200 golden rows (tests/golden/codebook_full.npz: against the oracle AND against the indices
 ``UMGMQuantizer.encode`` itself produced, codebook.py:106-131, 231-239, 330-337), on a codebook with DUPLICATED and NEARLY duplicated
 codewords (exact ties -- first index wins in the reference, codebook.py:110 ``argmin`` -- and gaps spread around the bound), and on other
-dictionary sizes.  The HIP kernels are held to the same statements in tests/test_hip_encode_two_stage.py."""
+dictionary sizes; then, on the hostile models and rows of tests/_encode_families.py, the proof's inequalities one by one (the bound on every
+cell, every collapsed score against a float64 chain, the kernel's integer ranges).  The HIP kernels are held to the same statements in
+tests/test_hip_encode_two_stage.py."""
 import copy
 
 import numpy as np
@@ -107,3 +109,140 @@ def test_refusals_and_the_grid():
     big["codebook/0/codebook"] = np.concatenate([st["codebook/0/codebook"], st["codebook/0/codebook"]])
     with pytest.raises(ValueError):
         candidate_tables(big, 3, 0.387, 0)
+    # the bias past 2^44 AFTER the grid choice: the grid keeps rint(g / h) below 2^44 - 2^32, but the folded input offset
+    # (128 - zx) * rowsum(G_int) comes on top -- up to 128 * 256 * 2^23 = 2^38.  A state built for it: level 0 with identity heads, one
+    # codeword -1 in every channel (a G row of +2 everywhere) and a quantization bias just large enough that g decides the grid.
+    import _encode_families as F
+    one = F.fewer_levels(st, 1)
+    one["codebook/0/stage_w"] = one["codebook/0/qhead_w"] = np.eye(256, dtype=np.float32)
+    cb = np.zeros((128, 256), np.float32)
+    cb[0] = -1.0
+    one["codebook/0/codebook"] = cb
+    one["codebook/0/stage_b"] = np.zeros(256, np.float32)
+    one["codebook/0/qhead_b"] = np.full(256, 4096.0, np.float32)
+    terms = F.h_terms(one, 1, 0.387)
+    assert max(terms, key=terms.get) == "bias" and terms["g"] > 0.5 * terms["bias"], terms
+    with pytest.raises(ValueError, match="fixed-point range"):
+        candidate_tables(one, 1, 0.387, 0)
+    assert candidate_tables(one, 1, 0.387, 128)["bias"].max() == 2 ** 44 - 2 ** 32     # (no folded offset at zx = 128: exactly the limit)
+    # (the table refusal, an entry >= 2^28 after the grid choice, cannot be reached with finite weights: h >= tmax / (2^28 - 2) puts the
+    #  largest entry ON 2^28 - 2 -- test_proof_inequalities_on_every_family asserts that on the two families whose tables decide)
+
+
+# ---- the proof's inequalities, stated directly, on hostile models and rows (tests/_encode_families.py) --------------------------------------
+# (a) an accepted cell equals the oracle; (b) |oracle gap - stage-1 gap| <= tau_l(N0) h on EVERY cell whose codes agree so far;
+# (c) every integer score against a float64 evaluation of the layered chain; (d) the kernel's integer ranges; (e) cells on both sides.
+_BASE, _FAMILIES = [], {}
+
+
+def _family(name, golden):
+    """(family, its candidate tables): built once per module -- candidate_tables is hundreds of 256 x 256 SVDs"""
+    import _encode_families as F
+    from quantv2x_amd.encode_two_stage import candidate_tables
+    if name not in _FAMILIES:
+        if not _BASE:
+            _BASE.append(_state())
+        fam = F.family(name, _BASE[0], golden["codebook_full"])
+        _FAMILIES[name] = (fam, candidate_tables(fam.state, fam.levels, fam.in_delta, fam.in_zx))
+    return _FAMILIES[name]
+
+
+def check_proof(fam, tabs, golden_u8):
+    import _encode_families as F
+    from oracle.spec import Oracle
+    from quantv2x_amd.encode_two_stage import candidate_emulate
+    rows, n_gold = F.hostile_rows(golden_u8, tabs, fam.in_zx)
+    h, levels = tabs["h"], fam.levels
+    cand, flagged, flags, gaps = candidate_emulate(rows, tabs, fam.in_delta, fam.in_zx)
+    want, ogaps = Oracle(fam.state).encode_rows(F.dequantized(rows, fam.in_delta, fam.in_zx), want_gaps=True)
+    assert cand.shape == want.shape == (levels, len(rows))
+    # (a) accepted == oracle, and an accepted cell is the fp32 chain's STRICT minimum
+    ok = ~flagged
+    wrong = (cand != want).any(0)
+    assert not (wrong & ok).any(), f"[{fam.name}] an ACCEPTED cell differs from the fp32 chain: rows {np.flatnonzero(wrong & ok)[:8]}"
+    assert (ogaps[:, ok] > 0).all()
+    # (b) both gaps are minima over b of quantities that differ by at most E_l + 2 e2 = tau_l h (module docstring of encode_two_stage.py);
+    # the oracle's gap is ONE more fp32 subtraction (second - best, oracle/qv2x_oracle.c): 2^-24 of it on top
+    tau = F.tau_units(tabs, rows, fam.in_delta, fam.in_zx)
+    slack = []
+    for l in range(levels):
+        same = (cand[:l + 1] == want[:l + 1]).all(0)
+        lhs = np.abs(ogaps[l].astype(np.float64) - gaps[l])
+        rhs = tau[l] * h + 2.0 ** -24 * ogaps[l].astype(np.float64)
+        bad = same & ~(lhs <= rhs)
+        assert not bad.any(), (f"[{fam.name}] level {l}: the bound does not cover the fp32 chain on rows {np.flatnonzero(bad)[:8]}: "
+                               f"|gap difference| {lhs[bad][:4]} > tau h {rhs[bad][:4]}")
+        slack.append(float((lhs[same] / (tau[l][same] * h)).max()) if same.any() else float("nan"))
+    # (c) stage 1's own error: h S_l[k] against the float64 chain with the oracle's codes forced.  e2 = 0.5 sum |code - zx| (G on the grid)
+    # + 0.5 (1 + l) (bias and l table entries) units; eps64 = the float64 chain's bound (F.chain_f64) TWICE -- the collapsed form is the same
+    # sum of the same products grouped differently, each passing through as many roundings -- plus the one rounding of h * S
+    x0 = (rows.astype(np.float64) - fam.in_zx) * fam.in_delta
+    n1 = np.abs(rows.astype(np.int64) - fam.in_zx).sum(1).astype(np.float64)
+    grid = []
+    for l, (sc, (val, err)) in enumerate(zip(F.integer_scores(tabs, rows, want), F.chain_f64(fam.state, levels, x0, want))):
+        e2 = (0.5 * n1 + 0.5 * (1 + l))[:, None] * h
+        lhs = np.abs(h * sc - val)
+        eps64 = 2.0 * err + F.U64 * np.abs(h * sc)
+        bad = ~(lhs <= e2 + eps64)
+        assert not bad.any(), (f"[{fam.name}] level {l}: {int(bad.sum())} collapsed scores leave the grid error: worst {float((lhs / (e2 + eps64)).max()):.3g} "
+                               f"of the bound at (row, k) {np.argwhere(bad)[:4].tolist()}")
+        grid.append(float((lhs / e2).max()))
+    # (d) the conditions of the kernel's comments (csrc/codebook_encode_cand.hip): i32 accumulators and bracket, fp64 packed scores
+    r = F.integer_ranges(tabs, rows, cand)
+    assert r["acc_analytic"] < 2 ** 31 and r["bracket_analytic"] < 2 ** 31 and r["packed_analytic"] < 2 ** 53, r
+    assert r["acc_attained"] <= r["acc_analytic"] and r["bracket_attained"] <= r["bracket_analytic"] and r["packed_attained"] <= r["packed_analytic"], r
+    stats = {"family": fam.name, "rows": len(rows), "decided_by": F.decided_by(fam.state, levels, fam.in_delta), "h": h,
+             "flagged_golden": float(flagged[:n_gold].mean()), "flagged_all": float(flagged.mean()),
+             "flagged_per_level": flags.mean(1).round(4).tolist(), "slack_ratio": [round(s, 5) for s in slack],
+             "grid_ratio": [round(s, 4) for s in grid], "bracket_bits": round(float(np.log2(max(1, r["bracket_attained"]))), 2),
+             "bracket_bits_analytic": round(float(np.log2(r["bracket_analytic"])), 2),
+             "packed_bits_analytic": round(float(np.log2(r["packed_analytic"])), 2)}
+    print("two-stage proof:", stats)
+    return stats, (rows, cand, want, flagged)
+
+
+def _families():
+    import _encode_families as F
+    return F.FAMILY_NAMES
+
+
+@pytest.mark.parametrize("name", _families())
+def test_proof_inequalities_on_every_family(golden, name):
+    import _encode_families as F
+    codes_u8, _ = golden_rows(golden["codebook_full"])
+    fam, tabs = _family(name, golden)
+    stats, (rows, cand, want, flagged) = check_proof(fam, tabs, codes_u8)
+    # (e) not vacuous: at least 5 % of the golden sample accepted (otherwise (a) says nothing), at least one cell flagged
+    assert stats["flagged_golden"] <= 0.95 and flagged.any(), stats
+    # the variants that exist to reach a branch of the grid choice must reach it
+    if name == "base":
+        assert fam.in_zx == 0                                            # (the (0, g) point of the issue's input quantizers)
+    if name in ("tables_decide_h", "delta_div16"):                       # (a small in_delta shrinks delta G: the tables decide there too)
+        terms = F.h_terms(fam.state, fam.levels, fam.in_delta)
+        assert max(terms, key=terms.get) == "tables" and tabs["h"] == terms["tables"], terms
+        assert np.abs(tabs["tables"]).max() == 2 ** 28 - 2               # the grid choice puts the largest table entry exactly on the limit
+    if name == "limb_extremes":
+        limbs = F.balanced_limbs(tabs["g_int"])
+        assert stats["decided_by"] == "g"
+        assert (limbs[0, :F.LIMB_ROWS] == -128).all() and (limbs[1, :F.LIMB_ROWS] == -128).all()
+        assert (limbs[:, F.LIMB_ROWS] == 127).all() and (limbs[:, F.LIMB_ROWS + 1] == -127).all()
+        # the all-zero row (stored bytes -128) against those rows: both low accumulators at 256 * 128 * 128, the bracket at 2^30 + 2^22
+        assert stats["bracket_bits"] >= 30.0 and F.integer_ranges(tabs, rows[:1] * 0, cand[:, :1])["acc_attained"] == 2 ** 22
+    if name in ("levels_1", "levels_2"):
+        assert tabs["tau"].shape == (fam.levels, 3) and tabs["gpack"].shape[0] == fam.levels and cand.shape[0] == fam.levels
+
+
+@pytest.mark.parametrize("name", ["heads_x0.05", "heads_x20", "bias_decides_h"])
+def test_families_that_must_flag_every_row(golden, name):
+    """Models the candidate stage can represent but not decide.  heads_x0.05 / heads_x20: the collapsed matrix of level l grows as
+    f^(4 l + 4), a factor f^8 between levels 0 and 2 on ONE 24-bit grid, so the small level's scores are all grid error.  bias_decides_h:
+    a bias entry 2^21 times the largest G entry decides the grid (asserted), the distances are that large and one fp32 ulp of them exceeds
+    the gaps.  Every golden row must be FLAGGED (stage 2 then decides: still exact) -- and (a)-(d) hold as everywhere."""
+    import _encode_families as F
+    codes_u8, _ = golden_rows(golden["codebook_full"])
+    fam, tabs = _family(name, golden)
+    stats, _ = check_proof(fam, tabs, codes_u8)
+    assert stats["flagged_golden"] == 1.0, stats
+    if name == "bias_decides_h":
+        terms = F.h_terms(fam.state, fam.levels, fam.in_delta)
+        assert max(terms, key=terms.get) == "bias" and tabs["h"] == terms["bias"], terms

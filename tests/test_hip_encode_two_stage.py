@@ -241,3 +241,120 @@ def test_stage2_alone_on_constructed_lists(golden, counts):
     torch.cuda.synchronize()
     bad = (work != ref.reshape(eng.levels, m_cells)).sum().item()
     assert bad == 0, f"{bad} indices differ after stage 2 on lists of {counts} cells"
+
+
+# ---- the hostile families of tests/_encode_families.py: the kernels held to the statements tests/test_encode_two_stage_cpu.py proves ------------
+def assert_stage1_is_the_emulation(eng, n, codes_u8, in_delta, in_zx):
+    """stage 1 alone = ``candidate_emulate`` bit for bit: every candidate index, the three lists as sets, the four counters (n0, n1 and
+    the in_zx arithmetic of the kernel are visible only through the listed set)"""
+    from quantv2x_amd.encode_two_stage import candidate_emulate
+    levels = eng.enc_levels
+    cand, listed, cnt, lists = stage1_alone(eng, n)
+    e_cand, e_flag, e_flags, _ = candidate_emulate(codes_u8, eng._two_stage[4], float(in_delta), int(in_zx))
+    assert np.array_equal(cand, e_cand), f"{int((cand != e_cand).sum())} candidate indices differ from the emulation"
+    assert np.array_equal(listed, np.flatnonzero(e_flag)), (len(listed), int(e_flag.sum()))
+    first = [e_flags[l] & ~e_flags[:l].any(0) for l in range(levels)] + [np.zeros_like(e_flag)] * (3 - levels)
+    assert cnt[0] == e_flag.sum() and list(cnt[1:4]) == [int(f.sum()) for f in first], (cnt, [int(f.sum()) for f in first])
+    for c in range(3):
+        assert np.array_equal(np.sort(lists[c]), np.flatnonzero(first[c])), c
+    return e_flag
+
+
+def _family_names():
+    import _encode_families as F
+    return F.FAMILY_NAMES + tuple(F.FLAG_EVERYTHING)
+
+
+@pytest.fixture(scope="module", params=_family_names())
+def deployed_family(request, golden):
+    """one deploy per family (the expensive part), alive for that family's tests only"""
+    import _encode_families as F
+    fam = F.family(request.param, _state(), golden["codebook_full"])
+    st, eng = v2xreal_engine(fam.state, {"in_delta": fam.in_delta, "in_zp": fam.in_zx})
+    yield fam, st, eng
+    del eng
+    torch.cuda.empty_cache()
+
+
+def test_every_family_two_stage_equals_exact_and_oracle_and_stage1_is_the_emulation(deployed_family, golden):
+    """The hostile rows in front of the golden rows, one V2X-Real frame of 35 200 cells: ``two_stage == exact == Oracle.encode_rows`` with 0
+    mismatches, and stage 1 alone is the numpy emulation the CPU proof is about.  Covers the grid step decided by a table entry and by a
+    bias entry, limbs of -128 against stored bytes of -128 (the kernel's i32 bracket at 2^30 + 2^22), one and two levels, in_zx 255 / 128,
+    in_delta / 16 and x 8, and the families the bound cannot decide (every cell listed)."""
+    import _encode_families as F
+    from oracle.spec import Oracle
+    fam, st, eng = deployed_family
+    assert eng.encode_mode == "two_stage" and eng.two_stage_refused is None and eng.enc_levels == fam.levels
+    assert (float(eng.shrink1.out_q[0]), int(eng.shrink1.out_q[1])) == (fam.in_delta, fam.in_zx)
+    codes_u8, _ = golden_rows(golden["codebook_full"])
+    rows = F.frame_rows(codes_u8, eng._two_stage[4], fam.in_zx, eng.fh * eng.fw)
+    put_rows(eng, 1, rows)
+    got = run_modes(eng, 1)
+    want = Oracle(st).encode_rows(F.dequantized(rows, fam.in_delta, fam.in_zx))
+    assert got["exact"].shape == want.shape == (fam.levels, len(rows))
+    assert np.array_equal(got["exact"], want), f"[{fam.name}] exact kernel: {int((got['exact'] != want).sum())} indices differ from the oracle"
+    mism = int((got["two_stage"] != want).sum())
+    assert mism == 0, f"[{fam.name}] two-stage encode: {mism} indices differ from the oracle"
+    e_flag = assert_stage1_is_the_emulation(eng, 1, rows, fam.in_delta, fam.in_zx)
+    stats = eng.encode_refine_stats(1)
+    print(f"two-stage encode [{fam.name}]:", stats)
+    assert stats["refined"] == int(e_flag.sum())
+    if fam.name in F.FLAG_EVERYTHING:                                  # (the golden rows behind the hostile ones are all listed)
+        assert e_flag[-30000:].all()
+
+
+def _big_launches():
+    """an engine whose cell count per frame (100 x 348 = 34 800 = 2^4 * 2175) makes neither kernel's launch a whole number of workgroups,
+    and the frame counts on both sides of the candidate kernel's switch to four cell tiles per wave (M >= 4 * CUs * 256)"""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    cells = 100 * 348
+    n_hi = -(-4 * cus * 256 // cells)
+    return cus, cells, n_hi
+
+
+@pytest.mark.parametrize("side", ["four_tiles", "two_tiles_just_below"])
+def test_candidate_kernel_both_tile_forms_at_a_large_ragged_launch(golden, side):
+    """``encode_candidates_kernel<4>`` (the bench batch's form, reached elsewhere only end to end) and ``<2>`` just below the switch, on a
+    launch whose last workgroup is partial: stage 1 == the emulation on EVERY cell, two_stage == exact."""
+    import _encode_families as F
+    g = golden["codebook_full"]
+    codes_u8, _ = golden_rows(g)
+    fam = F.family("base", _state(), g)
+    cus, cells, n_hi = _big_launches()
+    n = n_hi if side == "four_tiles" else n_hi - 1
+    assert n >= 1 and (n * cells >= 4 * cus * 256) == (side == "four_tiles")
+    assert (n * cells) % (512 if side == "four_tiles" else 256) != 0   # (a partial last workgroup: 128 | 64 cells per wave, four waves)
+    from quantv2x_amd.engine import deploy
+    eng = deploy(state=F.deployable(fam, (696, 200, 1)))
+    eng._workspace(n)
+    assert (eng.fh, eng.fw) == (100, 348) and eng.encode_mode == "two_stage"
+    rows = F.frame_rows(codes_u8, eng._two_stage[4], fam.in_zx, n * cells)
+    put_rows(eng, n, rows)
+    got = run_modes(eng, n)
+    mism = int((got["two_stage"] != got["exact"]).sum())
+    assert mism == 0, f"{mism} indices of {n} frames differ between the two-stage and the exact encode"
+    assert_stage1_is_the_emulation(eng, n, rows, fam.in_delta, fam.in_zx)
+
+
+def test_a_failing_operand_build_ends_in_the_exact_encode(golden, monkeypatch):
+    """Whatever ``candidate_tables`` raises -- not only the ValueError of its documented refusals -- the engine falls back to
+    ``encode_mode = "exact"`` with the reason in ``two_stage_refused``, and still encodes: no dead forward."""
+    import quantv2x_amd.encode_two_stage as E
+    from oracle.spec import Oracle
+    g = golden["codebook_full"]
+    codes_u8, rows = golden_rows(g)
+
+    def singular(*a, **k):
+        raise np.linalg.LinAlgError("SVD did not converge")
+
+    def arithmetic(*a, **k):
+        raise FloatingPointError("invalid value encountered in divide")
+
+    for boom in (singular, arithmetic):
+        monkeypatch.setattr(E, "candidate_tables", boom)
+        st, eng = v2xreal_engine(_state(), g)
+        assert eng.encode_mode == "exact" and eng.two_stage_refused and eng._two_stage is None, (eng.encode_mode, eng.two_stage_refused)
+        put_rows(eng, 1, codes_u8)
+        got = eng.encode_codes(1).cpu().numpy().reshape(3, -1)
+        assert np.array_equal(got, Oracle(st).encode_rows(rows))
+        del eng
