@@ -38,8 +38,9 @@ extern "C" {
 const char* qv2x_last_error(void);
 /* The ABI of this header.  A caller built against another value must not pass its structs: 5 = qv2x_encode_desc grew the trailing `segs`
  * field (round 5; a caller built before it passes garbage there unless its struct was zero-initialised -- ADVICE r5); 6 = round 6:
- * qv2x_codebook_encode_candidates_i8 / qv2x_codebook_encode_listed_f32 added, no struct changed. */
-#define QV2X_ABI_VERSION 6
+ * qv2x_codebook_encode_candidates_i8 / qv2x_codebook_encode_listed_f32 added, no struct changed; 7 =
+ * qv2x_codebook_encode_candidates_seg_i8 added and qv2x_codebook_encode_listed_f32 widened to seg_num 2 / dict_size 256, no struct changed. */
+#define QV2X_ABI_VERSION 7
 int qv2x_version(void);            /* == QV2X_ABI_VERSION of the library's own build */
 
 /* Fill a padded i8 BEV tensor (border AND interior) with one byte value: the per-frame canvas clear and the
@@ -243,6 +244,25 @@ int qv2x_codebook_encode_candidates_i8(const qv2x_encode_desc* desc /* host */, 
                                        void* stream);
 int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* desc /* host */, const int8_t* in, const float* const* level_weights /* host array */,
                                     const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream);
+
+/* Stage 1 for SEGMENTED and 256-entry codebooks: seg_num (desc->segs) 1 | 2, dict_size (desc->kc) a multiple of 32 up to 256 (of 64 with
+ * two segments), seg_num * dict_size <= 512, up to three levels.  qv2x_codebook_encode_candidates_i8 keeps its contract (it refuses these
+ * shapes); this entry has the same argument list and the same meaning, with ke = segs * kc scores per level -- the rows of the EXTENDED
+ * codebook, segment s in rows s * kc .. -- and an argmin, a (best, second) gap and a code plane PER SEGMENT:
+ *   g_limbs  i8  [levels][ke/32][3][8][64][16]: as above, score tile t of a level = scores 32 t .. of its ke
+ *   bias_packed f64 [levels*ke] = 256 * (rint(g / h) + (128 - zx) * rowsum(G_int)) + k,  k = the index INSIDE the segment (8 bits);
+ *            |rint(g / h) + ...| < 2^43: packed scores and their differences are exact below 2^53
+ *   tables   i32 [levels(levels-1)/2][ke][ke] = rint(T_lj / h): row s' * kc + code_{j, s'} (one row per segment of the earlier level j is
+ *            added), column s * kc + k; entries below 2^29 / max(2, segs * (levels - 1))
+ *   tau      f32 [levels][3], HOST: one bound per level, applied to every segment's gap
+ *   codes    u8 [levels * segs][n*h*w]: plane l * segs + s (the layout of qv2x_codebook_encode_f32)
+ *   list, counters: as above -- list c = the cells whose first undecided LEVEL is c (a level is undecided if any of its segments is).
+ * Stage 2 for these shapes is qv2x_codebook_encode_listed_f32 itself, WIDENED IN PLACE (no second entry): it takes seg_num 1 | 2 and
+ * dict_size up to 256 (seg_num * dict_size <= 512); a cell of list c reads its `segs` stored codes per level below c.  Its launches for
+ * seg_num 1, dict_size <= 128 are what they were. */
+int qv2x_codebook_encode_candidates_seg_i8(const qv2x_encode_desc* desc /* host */, const int8_t* in, const int8_t* g_limbs, const double* bias_packed,
+                                           const int32_t* tables, const float* tau /* host */, uint8_t* codes, uint32_t* list, uint32_t* counters,
+                                           void* stream);
 
 /* a7 + a8 + a9 + a10.  UMGMQuantizer.decode as three table look-ups (codebook.py:339-343; all heads affine),
  * warp_affine_simple (torch_transformation_utils.py:323-332: affine_grid + bilinear grid_sample, zeros,

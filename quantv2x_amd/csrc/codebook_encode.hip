@@ -224,7 +224,11 @@ __device__ __forceinline__ void encode_rows(const EncArgs& a, const int m0, floa
         if (proven) {
             head = gemm_head((const float2*)lhead_w, lhead_b, wave, lane);
             store_tile(bufB, wave, lane, acc);
-            if (tid < ER) code_s[tid] = (int)a.codes[(size_t)l * a.M + lst[m0 + tid < n_listed ? m0 + tid : n_listed - 1]];
+            // (code_s holds ROWS of the extended codebook: sg * kc + code, one per segment)
+            if (tid < ER * segs) {
+                const int sg = tid / ER, r = tid - sg * ER;
+                code_s[tid] = sg * a.kc + (int)a.codes[((size_t)l * segs + sg) * a.M + lst[m0 + r < n_listed ? m0 + r : n_listed - 1]];
+            }
             lds_barrier();
         } else {
         head = gemm_head((const float2*)qhead_w, qhead_b, wave, lane);
@@ -411,13 +415,15 @@ __global__ __launch_bounds__(512, ER == 32 ? 4 : 2) void codebook_encode_kernel(
 // `a.list_slots` persistent waves; what is left -- up to `a.list_tail_max` tiles of 32 cells, e.g. ALL of one frame's ~100 tiles -- runs here
 // as 8-wave workgroups, a third of a wave's latency (the same split qv2x_codebook_encode_f32 makes on the host; here both kernels derive it
 // from the DEVICE-side counts: codebook_encode.h:list_plan).
+// EXT: seg_num 2 or dict_size 256 (encode_rows' general variant); false is the form every (1, <= 128) model has always taken.
+template <bool EXT>
 __global__ __launch_bounds__(512, 2) void codebook_encode_list_tail_kernel(const EncArgs a) {      // (71 KB of LDS: two per CU whatever the registers)
     __shared__ __attribute__((aligned(16))) float smem[enc_smem_floats<32>()];
     const ListPlan plan = list_plan(a);
     for (int t = plan.full + (int)blockIdx.x; t < plan.total; t += (int)gridDim.x) {
         int cls, i0;
         list_tile(plan, t, cls, i0);                                    // list c: the cells first undecided at level c
-        encode_rows<32, false, true>(a, i0, smem, a.list + (size_t)cls * a.M, plan.n[cls], cls);
+        encode_rows<32, EXT, true>(a, i0, smem, a.list + (size_t)cls * a.M, plan.n[cls], cls);
         __syncthreads();
     }
 }
@@ -484,19 +490,21 @@ extern "C" int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* d, const 
     using namespace qv2x;
     if (!d || !in || !level_weights || !codes || !list || !list_count) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: null pointer");
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->levels < 1 || d->levels > 4) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: bad shape");
-    if (d->segs > 1) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: seg_num 1 only");
-    if (d->kc < 32 || d->kc > 256 || d->kc % 32) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: dict_size must be a multiple of 32 up to 256 (got %d)", d->kc);
+    const int segs = d->segs ? d->segs : 1;
+    if (segs != 1 && segs != 2) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: seg_num 1 or 2 (got %d)", d->segs);
+    if (d->kc < 32 || d->kc > 256 || d->kc % 32 || (segs > 1 && d->kc % 64) || segs * d->kc > 32 * ENC_MAX_TILES)
+        return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: dict_size must be a multiple of 32 up to 256 (of 64 with two segments): got %d x %d", segs, d->kc);
     if ((uintptr_t)in & 15) return fail(QV2X_EALIGN, "qv2x_codebook_encode_listed_f32: in must be 16-byte aligned");
     EncArgs a;
     a.in = in; a.in_f32 = nullptr; a.codes = codes; a.n = d->n; a.h = d->h; a.w = d->w; a.levels = d->levels; a.kc = d->kc;
-    a.segs = 1; a.ke = d->kc;
+    a.segs = segs; a.ke = segs * d->kc;
+    const bool ext = segs > 1 || a.ke > 128;                           // (as encode_launch: the workgroup form's general variant)
     a.ax = 128 - d->in_zx; a.dx = d->in_delta; a.M = d->n * d->h * d->w; a.m_lo = 0; a.m_hi = a.M;
     a.list = list; a.list_count = list_count;
     for (int l = 0; l < 4; ++l) {
         a.lvl[l] = l < d->levels ? level_weights[l] : nullptr;
         if (l < d->levels && (!a.lvl[l] || ((uintptr_t)a.lvl[l] & 15))) return fail(QV2X_EALIGN, "qv2x_codebook_encode_listed_f32: level %d weights null or unaligned", l);
     }
-    if (d->kc > 128) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: dict_size <= 128 (the candidate stage's contract)");
     int cus = 256, dev = 0, v = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
     const int tiles = (a.M + 31) / 32;
@@ -520,7 +528,8 @@ extern "C" int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* d, const 
     // slower: 145 against 97 us for one frame, 1164 against 940 us at the batch.  Every workgroup streams the same 2.7 MB of weights, and what
     // the launch waits for is that stream (~3-4 TB/s over the chip whatever the prefetch depth), not the matrix pipe:
     // tools/probes/codebook_encode_tail16_experiment.hip, profiles/r06_tail16_experiment.log)
-    codebook_encode_list_tail_kernel<<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
+    if (ext) codebook_encode_list_tail_kernel<true><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
+    else codebook_encode_list_tail_kernel<false><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
     return hip_check(hipGetLastError(), "qv2x_codebook_encode_listed_f32 launch");
 }
 

@@ -253,11 +253,13 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_
         if (LIST && l < start) {
             // a level whose code the candidate stage PROVED: no quantization head, no |q|^2, no distances -- the weight stream jumps to the
             // latent head (stage | qhead | codebook | lhead, 64 KiB per tile pair), the ring is primed again, the stored code is the code
-            wo = (8 + npair) * 65536;
+            // (SEGS > 1: the codebook part is the diagonal blocks only -- per pair of segments kc / 32 tile pairs of 32 / SEGS groups)
+            wo = SEGS == 1 ? (8 + npair) * 65536 : 8 * 65536 + (SEGS / 2) * (a.kc >> 5) * (32 / SEGS) * 2048;
             next_vec(lhead_b, 0);
 #pragma unroll
             for (int i = 0; i < 2 * NPF; ++i) ring[i] = wload(i);
-            bcs = a.codes[(size_t)l * a.M + mrow];
+#pragma unroll
+            for (int sg = 0; sg < SEGS; ++sg) bcs |= (unsigned)a.codes[((size_t)l * SEGS + sg) * a.M + mrow] << (8 * sg);
         } else {
         // ---- q = qhead(z) -------------------------------------------------------------------------------------------------
 #pragma unroll 1
@@ -424,8 +426,9 @@ int encode_wave_launch(const EncArgs& a, hipStream_t st) {
 
 // stage 2 of the two-stage encode: the listed cells, `waves` persistent single-wave workgroups (four per CU fill the chip)
 int encode_wave_list_launch(const EncArgs& a, int waves, hipStream_t st) {
-    if (a.segs != 1 || a.in_f32) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: seg_num 1, i8 rows");
-    codebook_encode_wave_kernel<false, 1, true><<<(unsigned)waves, 64, 0, st>>>(a);
+    if ((a.segs != 1 && a.segs != 2) || a.in_f32) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: seg_num 1 | 2, i8 rows");
+    if (a.segs == 2) codebook_encode_wave_kernel<false, 2, true><<<(unsigned)waves, 64, 0, st>>>(a);
+    else codebook_encode_wave_kernel<false, 1, true><<<(unsigned)waves, 64, 0, st>>>(a);
     return hip_check(hipGetLastError(), "qv2x_codebook_encode_listed_f32 launch");
 }
 

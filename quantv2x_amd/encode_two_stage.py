@@ -38,6 +38,12 @@ Measured on the bench's model: tau = 0.13 / 0.28 / 0.48 at levels 0 / 1 / 2 for 
 (the propagated part is ~1000x what the chain really loses -- worst-case rounding -- but the gaps are O(1), so it is affordable; tau as a
 whole is ~15x the largest gap difference measured).
 
+Segmented codebooks (seg_num m = 2) and 256 codes per segment (``segs`` below; csrc/codebook_encode_cand_seg.hip): the state holds the
+EXTENDED codebook [m kc][256], the collapsed form is the same with one argmin, one gap and one code plane PER SEGMENT, and level l adds
+m l table rows (one per segment of every earlier level) to a score.  ``encode_error_bound`` states what changes in the bound,
+``candidate_tables`` the integer ranges (packed score 256 S + k); tests/test_encode_two_stage_seg_cpu.py pins both.  Measured on the golden
+rows: 19.7 % of the cells listed at (2, 256), 9.4 % at (1, 256).
+
 ``tests/test_encode_two_stage_cpu.py`` pins the theory on the CPU: the numpy emulation of stage 1 (``candidate_emulate``) against the oracle
 on the reference's golden rows and on synthetic ones -- every accepted cell equal at every level, flagged fraction reported -- and, on the
 hostile models and rows of ``tests/_encode_families.py``, the inequality above on every cell, every score against a float64 chain, and the
@@ -74,10 +80,17 @@ class _Aff:
         return _Aff(self.p * c, self.r * c)
 
 
-def encode_error_bound(state: Dict[str, np.ndarray], levels: int, delta: float):
+def encode_error_bound(state: Dict[str, np.ndarray], levels: int, delta: float, segs: int = 1):
     """(ea, eb, ec) float64 [levels]: ``|(D_hat_l[a] - D_hat_l[b]) - (s_l[a] - s_l[b])| <= ea_l + eb_l N0 + ec_l N0^2`` for every pair of codes,
     every cell and every choice of the earlier levels' codes (see the module docstring; N0 = ||x_0||).  Also returns the per-source table
-    for DESIGN.md."""
+    for DESIGN.md.
+
+    ``segs`` = seg_num (m) > 1: the state's codebooks are the EXTENDED ones ([m kc][256], segment s in rows s kc .. and dims s d ..).  Two
+    statements change.  A comparison only ever happens between two codes of the SAME segment, so the pair sensitivity is maximised over
+    same-segment pairs of extended rows.  The codeword an earlier level subtracts is the SUM of one extended row per segment, so its part of
+    a norm bound is the sum over the segments of the per-segment maxima.  The kernels walk only the diagonal blocks (chains of d = 256 / m
+    terms for q . c_k and |q_s|^2, ||q_s|| <= ||q||): every partial sum of such a chain is one of the 256-long chain with its zero terms
+    left out, so the 256-long constants (``ub``, 256 ub cmax ||q||, X2 <= (1 + 2^-17) ||q||^2) bound them as they stand."""
     g = lambda l, n: state[f"codebook/{l}/{n}"].astype(np.float64)
     u1 = U / (1.0 - U)
     ub = u1 / (1.0 - 256.0 * u1)                                    # one 256-long chain, errors inside the partial sums included
@@ -87,7 +100,9 @@ def encode_error_bound(state: Dict[str, np.ndarray], levels: int, delta: float):
     ea, eb, ec, report = [], [], [], []
 
     def offset(shift, back):
-        return float(np.linalg.norm(shift) + sum(np.linalg.norm(g(j, "codebook") @ B.T, axis=1).max() for j, B in enumerate(back)))
+        # (the subtracted codeword of level j: one extended row per segment -- the per-segment maxima add up)
+        return float(np.linalg.norm(shift) + sum(sum(float(n.max()) for n in np.split(np.linalg.norm(g(j, "codebook") @ B.T, axis=1), segs))
+                                                 for j, B in enumerate(back)))
 
     def norm_bound(A, shift, back, srcs):
         d = _Aff()
@@ -111,10 +126,12 @@ def encode_error_bound(state: Dict[str, np.ndarray], levels: int, delta: float):
         e = _Aff()
         for M, eps, name in sq:
             # a comparison is about a PAIR of codes: (s_a - s_b) moves by 2 (c_a - c_b) . M delta <= 2 max_{a, b} ||M^T (c_a - c_b)|| ||delta||
-            K = Cb @ M
-            gram = K @ K.T
-            dg = np.diag(gram)
-            wpair = float(np.sqrt(max(0.0, (dg[:, None] + dg[None, :] - 2.0 * gram).max())))
+            # (segments: a and b belong to the same segment -- the maximum over the diagonal blocks of the pair matrix)
+            wpair = 0.0
+            for K in np.split(Cb @ M, segs):
+                gram = K @ K.T
+                dg = np.diag(gram)
+                wpair = max(wpair, float(np.sqrt(max(0.0, (dg[:, None] + dg[None, :] - 2.0 * gram).max()))))
             e = e + eps.scale(2.0 * wpair)
             report.append((l, name, wpair, eps.p, eps.r))
         # the terms each score has of its own, twice (a and b): the chain of q . c_k (partial sums <= ||c_k|| ||q||), 2 u |I_k|, the two
@@ -137,26 +154,47 @@ def encode_error_bound(state: Dict[str, np.ndarray], levels: int, delta: float):
     return np.array(ea) * host, np.array(eb) * host, np.array(ec) * host, report
 
 
-def candidate_tables(state: Dict[str, np.ndarray], levels: int, in_delta: float, in_zx: int) -> Dict[str, np.ndarray]:
-    """Everything ``qv2x_codebook_encode_candidates_i8`` reads (include/qv2x.h), from the frozen PTQ state:
+def pack_factor(segs: int, kc: int) -> int:
+    """the packed score is ``P S + k``: 128 where the index has seven bits (the first candidate kernel), 256 in the segment kernel"""
+    return 128 if segs == 1 and kc <= 128 else 256
 
-      gpack  i8  [levels][kc/32][LIMBS][8][64][16]  the limbs of G on the grid ``h`` as A fragments of v_mfma_i32_32x32x32_i8
+
+def candidate_tables(state: Dict[str, np.ndarray], levels: int, in_delta: float, in_zx: int, segs: int = 1) -> Dict[str, np.ndarray]:
+    """Everything ``qv2x_codebook_encode_candidates_i8`` (seg_num 1, dict_size <= 128) or ``qv2x_codebook_encode_candidates_seg_i8`` (seg_num
+    1 | 2, dict_size <= 256) reads (include/qv2x.h), from the frozen PTQ state; ke = segs * kc rows of the extended codebook per level:
+
+      gpack  i8  [levels][ke/32][LIMBS][8][64][16]  the limbs of G on the grid ``h`` as A fragments of v_mfma_i32_32x32x32_i8
                  (lane = 32 * half + score % 32, bytes = input channel 32 * step + 16 * half + 0..15)
-      bias   i64 [levels*kc]        rint(g / h) + (128 - zx) * rowsum(G_int): the kernel multiplies by the stored byte (code - 128)
-      tables i32 [levels(levels-1)/2][kc][kc]   rint(T_lj / h), table (l, j) at l (l - 1) / 2 + j
+      bias   i64 [levels*ke]        rint(g / h) + (128 - zx) * rowsum(G_int): the kernel multiplies by the stored byte (code - 128)
+      tables i32 [levels(levels-1)/2][ke][ke]   rint(T_lj / h), table (l, j) at l (l - 1) / 2 + j; row s' kc + code_{j, s'}, column s kc + k
       tau    f32 [levels][3]        tau_l / h = tau[l][0] + tau[l][1] N0 + tau[l][2] N0^2 (+ sum |code - zx|, added by the kernel)
-      h      the grid step (float64)"""
+      h      the grid step (float64)
+
+    The integer ranges.  A score is ``S = 65536 a2 + [256 a1 + a0 + sum of n_t table entries] + bias`` with |a_i| <= 256 * 128 * 128 = 2^22
+    (limb times stored byte, 256 terms) and n_t = segs * (levels - 1) table rows at the last level.  The bracket is an i32:
+    2^30 + 2^22 + n_t * tlim < 2^31 holds for tlim = 2^29 / max(2, n_t) (2^28 for one segment, 2^27 for two).  The packed score ``P S + k``
+    and the DIFFERENCE of two of them are exact in fp64 below 2^53: with |bias| < blim, |P S + k| < P (blim + 2^38 + 2^31) + P, so
+    blim = 2^44 at P = 128 (below 2^52) and 2^43 at P = 256 (the wider index costs one bit of bias).  The grid step coarsens until the
+    largest table and bias entries are inside; what still does not fit is refused."""
     from .engine import collapse_encoder_f64
-    G, gb, tabs = collapse_encoder_f64(state, levels)               # dist - |q|^2 = G x_0 + gb + tables, x_0 = delta (code - zx)
-    kc = G.shape[0] // levels
-    if kc % 32 or kc > 128 or levels > 3:
-        raise ValueError("two-stage encode: dict_size 32 | 64 | 96 | 128, up to three levels, seg_num 1")
+    G, gb, tabs = collapse_encoder_f64(state, levels)               # dist - |q_s|^2 = G x_0 + gb + tables, x_0 = delta (code - zx)
+    ke = G.shape[0] // levels
+    kc = ke // segs
+    if any(state[f"codebook/{l}/codebook"].shape[0] != ke for l in range(levels)):
+        raise ValueError("two-stage encode: every level needs the same dict_size")
+    if segs == 1:
+        if kc % 32 or kc > 256 or levels > 3:
+            raise ValueError("two-stage encode: dict_size 32 | 64 | 96 | 128 | ... | 256, up to three levels")
+    elif segs != 2 or kc * segs != ke or kc % 64 or kc > 256 or levels > 3:
+        raise ValueError("two-stage encode: seg_num 1 | 2, dict_size a multiple of 64 up to 256 with two segments, up to three levels")
+    n_t = segs * max(levels - 1, 0)
+    tlim = 2.0 ** 29 / max(2, n_t)
+    blim = 2.0 ** 44 if pack_factor(segs, kc) == 128 else 2.0 ** 43
     gs = float(in_delta) * G
-    # the grid: 24 bits for the largest entry of G -- coarser when a table or bias entry would leave the kernel's integer ranges (two table
-    # entries are added to 256 a1 + a0 in i32: below 2^28 each; the packed scores stay below 2^53: bias below 2^44).  A coarser grid only
-    # costs bound (e2 = 0.5 h sum |code - zx|), never exactness.
+    # the grid: 24 bits for the largest entry of G -- coarser when a table or bias entry would leave the kernel's integer ranges (above).  A
+    # coarser grid only costs bound (e2 = 0.5 h sum |code - zx|), never exactness.
     tmax = max([float(np.abs(t).max()) for t in tabs.values()] + [0.0])
-    h = max(float(np.abs(gs).max()) / G_MAX_INT, tmax / (2.0 ** 28 - 2.0), float(np.abs(gb).max()) / (2.0 ** 44 - 2.0 ** 32))
+    h = max(float(np.abs(gs).max()) / G_MAX_INT, tmax / (tlim - 2.0), float(np.abs(gb).max()) / (blim - 2.0 ** 32))
     gi = np.rint(gs / h).astype(np.int64)
     limbs, rest = [], gi.copy()
     for _ in range(LIMBS):
@@ -166,51 +204,60 @@ def candidate_tables(state: Dict[str, np.ndarray], levels: int, in_delta: float,
     if rest.any():
         raise ValueError("two-stage encode: G on the grid does not fit the candidate stage's int8 limbs")
     bias = np.rint(gb / h).astype(np.int64) + (128 - int(in_zx)) * gi.sum(1)
-    tables = np.stack([np.rint(tabs[(l, j)] / h) for l in range(levels) for j in range(l)]) if levels > 1 else np.zeros((1, kc, kc))
-    if np.abs(tables).max() >= 2 ** 28 or np.abs(bias).max() >= 2 ** 44:          # (the kernel adds two table entries to 256 a1 + a0 in i32)
+    tables = np.stack([np.rint(tabs[(l, j)] / h) for l in range(levels) for j in range(l)]) if levels > 1 else np.zeros((1, ke, ke))
+    if np.abs(tables).max() >= tlim or np.abs(bias).max() >= blim:
         raise ValueError("two-stage encode: table / bias entries leave the fixed-point range of the candidate stage")
     lane = np.arange(64)
-    score = (np.arange(levels * kc // 32)[:, None, None, None] * 32 + (lane & 31)[None, None, :, None])                  # [tiles, 1, 64, 1]
+    score = (np.arange(levels * ke // 32)[:, None, None, None] * 32 + (lane & 31)[None, None, :, None])                  # [tiles, 1, 64, 1]
     chan = (32 * np.arange(8)[None, :, None, None] + 16 * (lane >> 5)[None, None, :, None] + np.arange(16)[None, None, None, :])   # [1, 8, 64, 16]
-    packed = np.stack([lb[score, chan] for lb in limbs], axis=1)                           # [levels * kc / 32][limbs][8][64][16]
-    packed = packed.reshape(levels, kc // 32, LIMBS, 8, 64, 16)
-    ea, eb, ec, report = encode_error_bound(state, levels, in_delta)
+    packed = np.stack([lb[score, chan] for lb in limbs], axis=1)                           # [levels * ke / 32][limbs][8][64][16]
+    packed = packed.reshape(levels, ke // 32, LIMBS, 8, 64, 16)
+    ea, eb, ec, report = encode_error_bound(state, levels, in_delta, segs)
     fp = 1.0 + 1e-4                                                # the kernel evaluates tau in fp32 from N0 = delta * sqrt(n2) (a few ulp each)
     tau = np.zeros((levels, 3))
     for l in range(levels):
-        own = 1.0 + l + 2.0                                        # stage 1's own error, x 2: bias + tables half a unit each, + 1 unit of host slack
+        own = 1.0 + segs * l + 2.0                                 # stage 1's own error, x 2: bias + segs * l table entries half a unit each, + 1 unit of host slack
         tau[l] = [(ea[l] / h + own) * fp, eb[l] / h * fp, ec[l] / h * fp]
     return {"gpack": np.ascontiguousarray(packed, dtype=np.int8), "bias": np.ascontiguousarray(bias, dtype=np.int64),
             "tables": np.ascontiguousarray(tables, dtype=np.int32), "tau": np.ascontiguousarray(tau, dtype=np.float32), "h": h,
-            "g_int": gi, "bound": (ea, eb, ec), "report": report}
+            "g_int": gi, "bound": (ea, eb, ec), "report": report, "segs": segs, "kc": kc, "pack": pack_factor(segs, kc)}
 
 
 def candidate_emulate(codes_u8: np.ndarray, tabs: Dict[str, np.ndarray], in_delta: float, in_zx: int):
     """numpy emulation of stage 1 on rows of input codes u8 [R, 256] (exact: every integer stays below 2^53 in float64).  Returns
-    (codes u8 [levels, R], flagged bool [R], per-level flags bool [levels, R], gaps in score units f64 [levels, R])."""
+    (codes u8 [levels * segs, R] in the wire's plane order l * segs + s, flagged bool [R] -- a cell is listed if ANY plane is undecided --,
+    per-plane flags bool [levels * segs, R], gaps in score units f64 [levels * segs, R]).  The level a cell is first undecided at is the
+    first l with ``flags[l * segs:(l + 1) * segs].any(0)``."""
     gi, bias, tables, tau, h = tabs["g_int"], tabs["bias"], tabs["tables"], tabs["tau"], tabs["h"]
     levels = tau.shape[0]
-    kc = gi.shape[0] // levels
+    segs = int(tabs.get("segs", 1))
+    ke = gi.shape[0] // levels
+    kc = ke // segs
+    P = float(tabs.get("pack", 128))
     b = codes_u8.astype(np.float64) - 128.0
-    s = b @ gi.astype(np.float64).T + bias.astype(np.float64)[None]                      # [R, levels * kc], exact
+    s = b @ gi.astype(np.float64).T + bias.astype(np.float64)[None]                      # [R, levels * ke], exact
     n = codes_u8.astype(np.int64) - int(in_zx)
     n1, n2 = np.abs(n).sum(1), (n * n).sum(1)
     n0 = (np.float32(in_delta) * np.sqrt(n2.astype(np.float32))).astype(np.float32)
-    out = np.zeros((levels, codes_u8.shape[0]), np.uint8)
-    flags = np.zeros((levels, codes_u8.shape[0]), bool)
-    gaps = np.zeros((levels, codes_u8.shape[0]))
+    out = np.zeros((levels * segs, codes_u8.shape[0]), np.uint8)
+    flags = np.zeros((levels * segs, codes_u8.shape[0]), bool)
+    gaps = np.zeros((levels * segs, codes_u8.shape[0]))
     for l in range(levels):
-        sc = s[:, l * kc:(l + 1) * kc].copy()
+        sc = s[:, l * ke:(l + 1) * ke].copy()
         for j in range(l):
-            sc += tables[l * (l - 1) // 2 + j][out[j]].astype(np.float64)
-        order = np.argsort(sc, axis=1, kind="stable")
-        best, second = np.take_along_axis(sc, order[:, :1], 1)[:, 0], np.take_along_axis(sc, order[:, 1:2], 1)[:, 0]
-        out[l] = order[:, 0]
+            for sp in range(segs):
+                sc += tables[l * (l - 1) // 2 + j][sp * kc + out[j * segs + sp].astype(np.int64)].astype(np.float64)
         t = (((tau[l, 0] + tau[l, 1] * n0) + (tau[l, 2] * n0) * n0) + n1.astype(np.float32)).astype(np.float32)     # the kernel's fp32 statement
         assert t.dtype == np.float32 and n0.dtype == np.float32
         t = t.astype(np.float64)
-        # the kernel compares packed values 128 S + k: accepted iff second - best > 128 T + 127  (implies S_second - S_best > T)
-        k2 = np.take_along_axis(order, np.ones((len(sc), 1), np.int64), 1)[:, 0]
-        flags[l] = (128.0 * second + k2) - (128.0 * best + out[l]) <= 128.0 * np.ceil(t) + 127.0
-        gaps[l] = (second - best) * h
+        for sg in range(segs):
+            v = sc[:, sg * kc:(sg + 1) * kc]
+            order = np.argsort(v, axis=1, kind="stable")
+            best, second = np.take_along_axis(v, order[:, :1], 1)[:, 0], np.take_along_axis(v, order[:, 1:2], 1)[:, 0]
+            p = l * segs + sg
+            out[p] = order[:, 0]
+            # the kernel compares packed values P S + k: accepted iff second - best > P T + (P - 1)  (implies S_second - S_best > T)
+            k2 = order[:, 1]
+            flags[p] = (P * second + k2) - (P * best + out[p]) <= P * np.ceil(t) + (P - 1.0)
+            gaps[p] = (second - best) * h
     return out, flags.any(0), flags, gaps

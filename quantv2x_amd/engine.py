@@ -799,8 +799,11 @@ class DeployedModel(nn.Module):
         return codes
 
     def two_stage_supported(self) -> bool:
-        """seg_num 1, dict_size 32 | 64 | 96 | 128, up to three levels (qv2x_codebook_encode_candidates_i8's contract on i8 rows)"""
-        return bool(self.has_codebook and self.segs == 1 and self.kc <= 128 and self.kc % 32 == 0 and self.enc_levels <= 3)
+        """seg_num 1 with dict_size 32 | 64 | ... | 256, or seg_num 2 with dict_size 64 | 128 | 192 | 256, up to three levels: the contracts
+        of qv2x_codebook_encode_candidates_i8 (seg_num 1, dict_size <= 128) and qv2x_codebook_encode_candidates_seg_i8 (the rest) on i8 rows"""
+        if not self.has_codebook or self.enc_levels > 3 or self.kc > 256:
+            return False
+        return bool(self.kc % 32 == 0 if self.segs == 1 else self.segs == 2 and self.kc % 64 == 0)
 
     def _refuse_during_capture(self, what: str):
         if torch.cuda.is_current_stream_capturing():
@@ -812,13 +815,14 @@ class DeployedModel(nn.Module):
         outside the candidate stage's fixed-point contract (or ANY failure of the host algebra or the upload) leaves ``encode_mode = "exact"`` -- every cell through the
         chain, the same indices -- and says why in ``two_stage_refused``."""
         if not self.two_stage_supported():
-            raise NotImplementedError("encode_mode 'two_stage': seg_num 1, dict_size <= 128, up to three levels (encode_mode 'exact' takes the rest)")
+            raise NotImplementedError("encode_mode 'two_stage': seg_num 1 | 2, dict_size <= 256, up to three levels (encode_mode 'exact' takes the rest)")
         from .encode_two_stage import candidate_tables
         try:
-            t = candidate_tables(self.state, self.enc_levels, float(self.shrink1.out_q[0]), int(self.shrink1.out_q[1]))
-            k = np.arange(t["bias"].shape[0], dtype=np.int64) % self.kc
-            packed = (128 * t["bias"] + k).astype(np.float64)
-            if not np.array_equal(packed.astype(np.int64), 128 * t["bias"] + k):
+            t = candidate_tables(self.state, self.enc_levels, float(self.shrink1.out_q[0]), int(self.shrink1.out_q[1]), self.segs)
+            k = np.arange(t["bias"].shape[0], dtype=np.int64) % self.kc               # the index inside the segment
+            pf = int(t["pack"])                                          # 128 (the first candidate kernel) | 256 (the segment kernel)
+            packed = (pf * t["bias"] + k).astype(np.float64)
+            if not np.array_equal(packed.astype(np.int64), pf * t["bias"] + k):
                 raise ValueError("two-stage encode: packed scores not exact in float64")                  # (below 2^53 by construction)
             self._two_stage = (_dev(t["gpack"], self.dev), _dev(packed, self.dev), _dev(t["tables"], self.dev),
                                (C.c_float * (3 * self.enc_levels))(*[float(v) for v in t["tau"].reshape(-1)]), t)
@@ -826,12 +830,13 @@ class DeployedModel(nn.Module):
             self.encode_mode, self.two_stage_refused = "exact", str(e) or type(e).__name__
 
     def _encode_two_stage(self, d, b, codes):
-        """a6 as two launches (encode_two_stage.py): qv2x_codebook_encode_candidates_i8 decides every cell it can PROVE, the listed rest
-        goes through the reference-order kernel (qv2x_codebook_encode_listed_f32) -- identical indices, ~a tenth of the fp32 work."""
+        """a6 as two launches (encode_two_stage.py): qv2x_codebook_encode_candidates_i8 (seg_num 1, dict_size <= 128) or
+        qv2x_codebook_encode_candidates_seg_i8 (two segments, 256 codes) decides every cell it can PROVE, the listed rest goes through the
+        reference-order kernel (qv2x_codebook_encode_listed_f32) -- identical indices, a fraction of the fp32 work."""
         gp, bias, tab, tau, _ = self._two_stage
-        L.check(self.lib.qv2x_codebook_encode_candidates_i8(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
-                                                            L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()),
-                "qv2x_codebook_encode_candidates_i8")
+        name = "qv2x_codebook_encode_candidates_i8" if self.segs == 1 and self.kc <= 128 else "qv2x_codebook_encode_candidates_seg_i8"
+        L.check(getattr(self.lib, name)(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
+                                        L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), name)
         L.check(self.lib.qv2x_codebook_encode_listed_f32(C.byref(d), L.ptr(b["s1"]), self.level_ptrs, L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]),
                                                          L.ptr(codes), L.current_stream()), "qv2x_codebook_encode_listed_f32")
         return codes
