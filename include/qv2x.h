@@ -40,7 +40,7 @@ const char* qv2x_last_error(void);
  * field (round 5; a caller built before it passes garbage there unless its struct was zero-initialised -- ADVICE r5); 6 = round 6:
  * qv2x_codebook_encode_candidates_i8 / qv2x_codebook_encode_listed_f32 added, no struct changed; 7 =
  * qv2x_codebook_encode_candidates_seg_i8 added and qv2x_codebook_encode_listed_f32 widened to seg_num 2 / dict_size 256, no struct changed. */
-#define QV2X_ABI_VERSION 7
+#define QV2X_ABI_VERSION 8
 int qv2x_version(void);            /* == QV2X_ABI_VERSION of the library's own build */
 
 /* Fill a padded i8 BEV tensor (border AND interior) with one byte value: the per-frame canvas clear and the
@@ -624,6 +624,44 @@ int qv2x_pairwise_from_poses_f64(const uint8_t* gathered, int world, int64_t age
  * writes pairwise + f * max_cav * max_cav * 16. */
 int qv2x_pairwise_from_poses_batch_f64(const uint8_t* gathered, int world, int64_t agent_stride_bytes, int64_t pose_offset_bytes,
                                        int frames, int64_t frame_stride_bytes, int max_cav, double* pairwise, void* stream);
+
+/* ---- the ego's post stage in horizontal bands (one band per rank; quantv2x_amd/dist.py, shard_post) ---------------------------
+ * The reference's fusion has no cross-cell term (fusion_in_one.py:126-151: warp, per-cell softmax over the agents) and its heads are 1x1
+ * (heter_model_baseline.py:242-260), so the ego's maps can be computed in disjoint row bands and put together afterwards.  A band is the
+ * cell range [cell0, cell0 + n_cells) of every scene's h * w map (cell0 = y0 * w); its outputs are COMPACT: n_cells where the whole-map
+ * calls have h * w.  A cell's arithmetic is that of the whole-map call -- its sampling grid comes from its global coordinates, its fma /
+ * MFMA chain runs over its own row -- so a band equals the same cells of the whole-map call bit for bit, for any cell0 and n_cells.
+ * A range outside the map is QV2X_EINVAL; n_cells = 0 (an empty band: more ranks than rows) is QV2X_OK without a launch.
+ *
+ * The wire of a band's predictions: fp32 values, or the output quantizer's u8 codes (a quarter of the bytes): the heads' result IS
+ * (code - za) * da, so the receiver's dequantization gives the same bits.  The u8 wire needs a quantizer on every channel: `da_host`, the
+ * caller's host copy of da [cout], must be > 0 throughout, else QV2X_EINVAL (ignored, may be null, for QV2X_WIRE_F32). */
+#define QV2X_WIRE_F32 0
+#define QV2X_WIRE_U8 1
+/* qv2x_fuse_att_batch_f32 on a band: fused f32 [n_scenes][n_cells][256] (AttFusion.forward's loop over record_len, fusion_in_one.py:131-151,
+ * restricted to the band's ego cells). */
+int qv2x_fuse_att_band_f32(const qv2x_fuse_desc* desc /* host */, int n_scenes, const int64_t* scene_offset /* host */,
+                           const int32_t* scene_agents /* host */, const uint8_t* codes, const float* lut, const float* lut_bias,
+                           const float* feats, const double* pairwise, int64_t cell0, int64_t n_cells, float* fused, void* stream);
+/* qv2x_heads_f32 on a band's fused rows x f32 [n_scenes][n_cells][256] (heter_model_baseline.py:242-260): out NCHW [n_scenes][cout][n_cells],
+ * f32 values or u8 codes by `wire`. */
+int qv2x_heads_band(const float* x, int n_scenes, int64_t n_cells, int cout, int cout_pad, const float* w, const float* bias,
+                    const float* da, const float* za, int wire, const float* da_host /* host */, void* out, void* stream);
+/* qv2x_fuse_heads_batch_f32 on a band, a7-a11 in one launch: out NCHW [n_scenes][cout][n_cells], f32 values or u8 codes by `wire`;
+ * `fused_tap` (optional) f32 [n_scenes][n_cells][256]. */
+int qv2x_fuse_heads_band(const qv2x_fuse_desc* desc /* host */, int n_scenes, const int64_t* scene_offset /* host */,
+                         const int32_t* scene_agents /* host */, const uint8_t* codes, const float* lut, const float* lut_bias,
+                         const float* feats, const double* pairwise, int64_t cell0, int64_t n_cells, int cout, int cout_pad,
+                         const float* w, const float* bias, const float* da, const float* za, int wire, const float* da_host /* host */,
+                         void* out, float* fused_tap, void* stream);
+/* The gathered bands -> the ego's whole prediction maps (what the heads of heter_model_baseline.py:242-260 return on the whole fused map).
+ *   slabs [world][slab_bytes]: rank r's slab is its band [frames][cout][n_cells_r] (f32 or u8 by `wire`), then padding;
+ *         n_cells_r = ((r + 1) * h / world - r * h / world) * w, rows [r * h / world, (r + 1) * h / world) -- derived here, not sent;
+ *         slab_bytes >= frames * cout * ceil(h / world) * w elements, a multiple of 16; slabs and out 16-byte aligned
+ *   out   f32 [frames][cout][h * w]: a copy (f32) or (code - za[c]) * da[c] (u8; da, za device f32 [cout])
+ * One launch; world * frames * cout <= 65535. */
+int qv2x_assemble_bands(const uint8_t* slabs, int world, int64_t slab_bytes, int frames, int cout, int h, int w, int wire,
+                        const float* da, const float* za, float* out, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

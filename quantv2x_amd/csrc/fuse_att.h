@@ -14,6 +14,10 @@ struct FuseArgs {
     int fusion;                      // 0 = AttFusion, 1 = MaxFusion
     long long code_agent_stride, code_level_stride;
     double hm, wm, ratio;            // metres covered by the map (H, W) and discrete_ratio of normalize_pairwise_tfm
+    // The ego cells a launch computes: [cell0, cell0 + n_cells) of every scene's h * w map (a horizontal band, cell0 = y0 * w), written
+    // COMPACT -- row / column `local` of n_cells per scene.  The whole map is cell0 = 0, n_cells = hw.  The sampling grid and the taps are
+    // functions of the GLOBAL cell, so a cell's result does not depend on the band it is computed in.
+    int cell0, n_cells;
 };
 
 // one row of the decode table (row = plane * kc + code): 1 KiB, a float4 per lane
@@ -211,8 +215,10 @@ struct SceneList { long long off[MAX_SCENES]; int agents[MAX_SCENES]; };
 // host: smallest compiled bound that covers `agents`
 inline int fuse_bound(int agents) { return agents <= 1 ? 1 : (agents <= 2 ? 2 : (agents <= 4 ? 4 : MAXA)); }
 
-// shared argument checks + FuseArgs from the public descriptor (host)
+// shared argument checks + FuseArgs from the public descriptor (host); the cell range is the whole map
 int fuse_args_from_desc(const qv2x_fuse_desc* d, const uint8_t* codes, const float* lut, const float* lut_bias, const float* feats,
                         const double* pairwise, const char* who, FuseArgs& a);
+// the band entry points' range check (host): 0 <= cell0, 0 <= n_cells, cell0 + n_cells <= h * w; sets a.cell0 / a.n_cells
+int fuse_band_range(const char* who, long long cell0, long long n_cells, FuseArgs& a);
 
 }  // namespace qv2x

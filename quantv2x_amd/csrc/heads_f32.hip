@@ -23,6 +23,10 @@ namespace qv2x {
 //                workgroups = one round of the chip: a launch lasts as long as one tile's dependent chain, 62.8 against 24.0 + 31.7 us) and
 //                dropped it; a batch of 32 frames is 27 rounds, where what counts is throughput and the 2.3 GB of map traffic.  Same
 //                arithmetic as the two launches, bit for bit.  `fused_tap` (optional) still receives the rows (debug / parity tests).
+//                A launch may cover a BAND of every scene's map (FuseArgs::cell0, h.hw = the band's cells): row m is cell cell0 + m % h.hw,
+//                the output is the compact NCHW band.
+// U8 (the band entry points' u8 wire): the output element is the quantizer's CODE q_code(y, d, z) as a byte instead of its dequantized value
+// (code - z) * d -- the same code, so (float(byte) - z) * d on the receiving side is the fp32 output bit for bit.
 enum { ROWS_GLOBAL = 0, ROWS_DECODE = 2, ROWS_FUSE = 3 };
 
 #ifdef QV2X_HEADS_TRACE     // dev build only (s_memtime stamps, round 2): s_memtime stamps of thread 0 of every workgroup
@@ -37,7 +41,7 @@ struct HeadArgs {
     const float* w; const float* bias; const float* da; const float* za; float* out;
 };
 
-template <int SRC, int NA = 1>
+template <int SRC, int NA = 1, bool U8 = false>
 __device__ __forceinline__ void rows_heads_tile(const HeadArgs& h, const FuseArgs& fa, const int tm, float* smem, const SceneList* sl = nullptr) {
     float* rows = smem;
     HTRACE(0);
@@ -62,7 +66,7 @@ __device__ __forceinline__ void rows_heads_tile(const HeadArgs& h, const FuseArg
             m = __builtin_amdgcn_readfirstlane(m);
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (m < h.R) {
-                const int sc = m / h.hw, cell = m - sc * h.hw;
+                const int sc = m / h.hw, cell = fa.cell0 + (m - sc * h.hw);
                 FuseArgs a = fa;                               // this row's scene: its agents, where their data starts, its pairwise block
                 a.agents = sl->agents[sc];
                 if (a.feats) a.feats = (const float4*)((const float*)a.feats + sl->off[sc]);
@@ -211,7 +215,7 @@ __device__ __forceinline__ void rows_heads_tile(const HeadArgs& h, const FuseArg
 #pragma unroll
                 for (int r2 = 0; r2 < 4; ++r2) {
                     float y = c16[hf][r2];
-                    if (d > 0.0f) y = (q_code(y, d, z) - z) * d;
+                    if (d > 0.0f) y = U8 ? q_code(y, d, z) : (q_code(y, d, z) - z) * d;
                     tr[16 * hf + 4 * (lane >> 4) + r2][lane & 15] = y;
                 }
         } else {
@@ -220,7 +224,7 @@ __device__ __forceinline__ void rows_heads_tile(const HeadArgs& h, const FuseArg
 #pragma unroll
             for (int r2 = 0; r2 < 16; ++r2) {
                 float y = acc[r2];
-                if (d > 0.0f) y = (q_code(y, d, z) - z) * d;
+                if (d > 0.0f) y = U8 ? q_code(y, d, z) : (q_code(y, d, z) - z) * d;
                 tr[mfma32_row(r2, lane)][lane & 31] = y;
             }
         }
@@ -230,26 +234,30 @@ __device__ __forceinline__ void rows_heads_tile(const HeadArgs& h, const FuseArg
         const int mm = tm * 32 + (lane & 31);
         const int bi = mm / h.hw, cell = mm - bi * h.hw;
         float* ob = h.out + (size_t)bi * h.cout * h.hw + cell;
+        uint8_t* ob8 = (uint8_t*)h.out + (size_t)bi * h.cout * h.hw + cell;     // (U8: an integral float in [0, 255] converts exactly)
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
             const int ch = ct * 32 + par + 2 * c;
-            if (ch < h.cout && mm < h.R) ob[(size_t)ch * h.hw] = tr[lane & 31][par + 2 * c];
+            if (ch < h.cout && mm < h.R) {
+                if (U8) ob8[(size_t)ch * h.hw] = (uint8_t)tr[lane & 31][par + 2 * c];
+                else ob[(size_t)ch * h.hw] = tr[lane & 31][par + 2 * c];
+            }
         }
     }
     HTRACE(4);
 }
 
-template <int SRC>
+template <int SRC, bool U8 = false>
 __global__ __launch_bounds__(256) void rows_heads_kernel(const HeadArgs h, const FuseArgs fa) {
     __shared__ __attribute__((aligned(16))) float smem[32 * 256];
-    rows_heads_tile<SRC>(h, fa, blockIdx.x, smem);
+    rows_heads_tile<SRC, 1, U8>(h, fa, blockIdx.x, smem);
 }
 
 // a7-a11 in one launch: every 32-cell tile is fused (decode + warp + attention) and multiplied by the heads where it stands
-template <int NA>
+template <int NA, bool U8 = false>
 __global__ __launch_bounds__(256) void fuse_heads_kernel(const HeadArgs h, const FuseArgs fa, const SceneList sl) {
     __shared__ __attribute__((aligned(16))) float smem[32 * 256];
-    rows_heads_tile<ROWS_FUSE, NA>(h, fa, blockIdx.x, smem, &sl);
+    rows_heads_tile<ROWS_FUSE, NA, U8>(h, fa, blockIdx.x, smem, &sl);
 }
 
 // The fused-feature heads (rows from memory) and the *_single heads (rows decoded from the codes) of one frame in ONE
@@ -275,6 +283,57 @@ static int head_args(const char* who, int R, int hw, int cout, int cout_pad, con
     if ((uintptr_t)w & 15) return fail(QV2X_EALIGN, "%s: w must be 16-byte aligned", who);
     h.x = nullptr; h.R = R; h.hw = hw; h.cout = cout; h.cout_pad = cout_pad; h.w = w; h.bias = bias; h.da = da; h.za = za; h.out = out;
     return QV2X_OK;
+}
+
+// The band entry points' wire (host): QV2X_WIRE_F32, or QV2X_WIRE_U8 -- only when EVERY channel has an output quantizer, which the caller
+// shows with its host copy of `da` (the device array cannot be read under stream capture).
+static int wire_check(const char* who, int wire, int cout, const float* da_host) {
+    if (wire != QV2X_WIRE_F32 && wire != QV2X_WIRE_U8) return fail(QV2X_EINVAL, "%s: wire %d (QV2X_WIRE_F32 or QV2X_WIRE_U8)", who, wire);
+    if (wire == QV2X_WIRE_U8) {
+        if (!da_host) return fail(QV2X_EINVAL, "%s: the u8 wire needs da_host (the host copy of da)", who);
+        for (int c = 0; c < cout; ++c)
+            if (!(da_host[c] > 0.0f)) return fail(QV2X_EINVAL, "%s: the u8 wire needs an output quantizer on every channel (da[%d] = %g)", who, c, da_host[c]);
+    }
+    return QV2X_OK;
+}
+
+// The gathered band slabs [world][slab_bytes] (rank r: compact [planes][n_cells_r] f32 or u8 codes, its rows [r h / world, (r + 1) h / world)
+// of every plane; planes = frames * cout) -> the whole maps f32 [planes][h * w]: a copy, or the dequantization (code - z) * d.
+// blockIdx.y = (rank, plane): one contiguous run of n_cells_r elements each.  16-byte stores (and 16-byte / one-dword loads) over the part of
+// the run where source and destination are aligned alike -- always, when w % 4 == 0 -- and element by element over its ragged ends.
+template <bool U8>
+__global__ __launch_bounds__(256) void assemble_bands_kernel(const uint8_t* __restrict__ slabs, long long slab_bytes, int world, int planes, int cout,
+                                                             int h, int w, const float* __restrict__ da, const float* __restrict__ za,
+                                                             float* __restrict__ out) {
+    const int r = blockIdx.y / planes, p = blockIdx.y - r * planes;
+    const int y0 = (int)((long long)r * h / world), y1 = (int)((long long)(r + 1) * h / world);
+    const int n = (y1 - y0) * w;
+    if (n == 0) return;
+    const size_t so = (size_t)p * n;                                  // elements into the rank's slab
+    const uint8_t* s8 = slabs + (size_t)r * slab_bytes + so;
+    const float* s32 = (const float*)(slabs + (size_t)r * slab_bytes) + so;
+    const size_t dof = (size_t)p * h * w + (size_t)y0 * w;
+    float* dst = out + dof;
+    float d = 1.0f, z = 0.0f;
+    if (U8) { const int c = p % cout; d = da[c]; z = za[c]; }
+    auto one = [&](int i) __attribute__((always_inline)) { return U8 ? ((float)s8[i] - z) * d : s32[i]; };
+    int head = (int)((4 - (dof & 3)) & 3);                            // elements up to the destination's 16-byte boundary
+    if (head > n || ((so + head) & 3)) head = n;                      // (source not aligned alike: the whole run element by element)
+    const int nv = (n - head) >> 2;
+    const int tid = blockIdx.x * 256 + threadIdx.x, nt = gridDim.x * 256;
+    for (int i = tid; i < head; i += nt) dst[i] = one(i);
+    for (int v = tid; v < nv; v += nt) {
+        const int i = head + 4 * v;
+        float4 o;
+        if (U8) {
+            const unsigned cw = *(const unsigned*)(s8 + i);
+            o = make_float4(((float)(cw & 0xff) - z) * d, ((float)((cw >> 8) & 0xff) - z) * d, ((float)((cw >> 16) & 0xff) - z) * d, ((float)(cw >> 24) - z) * d);
+        } else {
+            o = *(const float4*)(s32 + i);
+        }
+        *(float4*)(dst + i) = o;
+    }
+    for (int i = head + 4 * nv + tid; i < n; i += nt) dst[i] = one(i);
 }
 
 __global__ __launch_bounds__(256) void decode_lut_kernel(const uint8_t* __restrict__ codes, int R, int levels, int kc,
@@ -423,12 +482,12 @@ extern "C" int qv2x_heads_f32(const float* x, int R, int hw, int cout, int cout_
     return hip_check(hipGetLastError(), "qv2x_heads_f32 launch");
 }
 
-extern "C" int qv2x_fuse_heads_batch_f32(const qv2x_fuse_desc* d, int n_scenes, const int64_t* scene_offset, const int32_t* scene_agents,
-                                         const uint8_t* codes, const float* lut, const float* lut_bias, const float* feats, const double* pairwise,
-                                         int cout, int cout_pad, const float* w, const float* bias, const float* da, const float* za,
-                                         float* out, float* fused_tap, void* stream) {
-    using namespace qv2x;
-    const char* who = "qv2x_fuse_heads_batch_f32";
+namespace qv2x {
+// qv2x_fuse_heads_batch_f32 and its band form: the same kernel, the cell range in FuseArgs and HeadArgs::hw = the band's cells
+static int fuse_heads_launch(const char* who, const qv2x_fuse_desc* d, int n_scenes, const int64_t* scene_offset, const int32_t* scene_agents,
+                             const uint8_t* codes, const float* lut, const float* lut_bias, const float* feats, const double* pairwise,
+                             const long long* range, int cout, int cout_pad, const float* w, const float* bias, const float* da, const float* za,
+                             bool u8, void* out, float* fused_tap, void* stream) {
     if (!scene_offset || !scene_agents || !d) return fail(QV2X_EINVAL, "%s: null pointer", who);
     if (n_scenes < 1 || n_scenes > MAX_SCENES) return fail(QV2X_EINVAL, "%s: 1..%d scenes, got %d", who, MAX_SCENES, n_scenes);
     SceneList sl{};
@@ -443,18 +502,89 @@ extern "C" int qv2x_fuse_heads_batch_f32(const qv2x_fuse_desc* d, int n_scenes, 
     d1.agents = most;
     FuseArgs a;
     if (int rc = fuse_args_from_desc(&d1, codes, lut, lut_bias, feats, pairwise, who, a)) return rc;
+    if (range) {
+        if (int rc = fuse_band_range(who, range[0], range[1], a)) return rc;
+        if (!out) return fail(QV2X_EINVAL, "%s: null pointer", who);
+        if (a.n_cells == 0) return QV2X_OK;                            // an empty band (world > h): nothing to launch
+    }
     a.fused = (float4*)fused_tap;
     HeadArgs h;
-    if (int rc = head_args(who, n_scenes * a.hw, a.hw, cout, cout_pad, w, bias, da, za, out, h)) return rc;
+    if (int rc = head_args(who, n_scenes * a.n_cells, a.n_cells, cout, cout_pad, w, bias, da, za, (float*)out, h)) return rc;
     const dim3 grid((h.R + 31) / 32);
     hipStream_t st = (hipStream_t)stream;
+    if (u8) {
+        switch (fuse_bound(most)) {
+            case 1: fuse_heads_kernel<1, true><<<grid, 256, 0, st>>>(h, a, sl); break;
+            case 2: fuse_heads_kernel<2, true><<<grid, 256, 0, st>>>(h, a, sl); break;
+            case 4: fuse_heads_kernel<4, true><<<grid, 256, 0, st>>>(h, a, sl); break;
+            default: fuse_heads_kernel<MAXA, true><<<grid, 256, 0, st>>>(h, a, sl); break;
+        }
+        return hip_check(hipGetLastError(), who);
+    }
     switch (fuse_bound(most)) {
         case 1: fuse_heads_kernel<1><<<grid, 256, 0, st>>>(h, a, sl); break;
         case 2: fuse_heads_kernel<2><<<grid, 256, 0, st>>>(h, a, sl); break;
         case 4: fuse_heads_kernel<4><<<grid, 256, 0, st>>>(h, a, sl); break;
         default: fuse_heads_kernel<MAXA><<<grid, 256, 0, st>>>(h, a, sl); break;
     }
-    return hip_check(hipGetLastError(), "qv2x_fuse_heads_batch_f32 launch");
+    return hip_check(hipGetLastError(), who);
+}
+}  // namespace qv2x
+
+extern "C" int qv2x_fuse_heads_batch_f32(const qv2x_fuse_desc* d, int n_scenes, const int64_t* scene_offset, const int32_t* scene_agents,
+                                         const uint8_t* codes, const float* lut, const float* lut_bias, const float* feats, const double* pairwise,
+                                         int cout, int cout_pad, const float* w, const float* bias, const float* da, const float* za,
+                                         float* out, float* fused_tap, void* stream) {
+    return qv2x::fuse_heads_launch("qv2x_fuse_heads_batch_f32", d, n_scenes, scene_offset, scene_agents, codes, lut, lut_bias, feats, pairwise, nullptr,
+                                   cout, cout_pad, w, bias, da, za, false, out, fused_tap, stream);
+}
+
+extern "C" int qv2x_fuse_heads_band(const qv2x_fuse_desc* d, int n_scenes, const int64_t* scene_offset, const int32_t* scene_agents,
+                                    const uint8_t* codes, const float* lut, const float* lut_bias, const float* feats, const double* pairwise,
+                                    int64_t cell0, int64_t n_cells, int cout, int cout_pad, const float* w, const float* bias, const float* da,
+                                    const float* za, int wire, const float* da_host, void* out, float* fused_tap, void* stream) {
+    using namespace qv2x;
+    if (int rc = wire_check("qv2x_fuse_heads_band", wire, cout, da_host)) return rc;
+    const long long range[2] = {(long long)cell0, (long long)n_cells};
+    return fuse_heads_launch("qv2x_fuse_heads_band", d, n_scenes, scene_offset, scene_agents, codes, lut, lut_bias, feats, pairwise, range,
+                             cout, cout_pad, w, bias, da, za, wire == QV2X_WIRE_U8, out, fused_tap, stream);
+}
+
+extern "C" int qv2x_heads_band(const float* x, int n_scenes, int64_t n_cells, int cout, int cout_pad, const float* w, const float* bias,
+                               const float* da, const float* za, int wire, const float* da_host, void* out, void* stream) {
+    using namespace qv2x;
+    const char* who = "qv2x_heads_band";
+    if (int rc = wire_check(who, wire, cout, da_host)) return rc;
+    if (!x || !out) return fail(QV2X_EINVAL, "%s: null pointer", who);
+    if (n_scenes < 1 || n_cells < 0 || n_cells * n_scenes > 0x7fffffffLL) return fail(QV2X_EINVAL, "%s: %d scenes of %lld cells", who, n_scenes, (long long)n_cells);
+    if (n_cells == 0) return QV2X_OK;                                  // an empty band: nothing to launch
+    HeadArgs h;
+    if (int rc = head_args(who, (int)(n_scenes * n_cells), (int)n_cells, cout, cout_pad, w, bias, da, za, (float*)out, h)) return rc;
+    if ((uintptr_t)x & 15) return fail(QV2X_EALIGN, "%s: x must be 16-byte aligned", who);
+    h.x = x;
+    if (wire == QV2X_WIRE_U8) rows_heads_kernel<ROWS_GLOBAL, true><<<(h.R + 31) / 32, 256, 0, (hipStream_t)stream>>>(h, FuseArgs{});
+    else rows_heads_kernel<ROWS_GLOBAL><<<(h.R + 31) / 32, 256, 0, (hipStream_t)stream>>>(h, FuseArgs{});
+    return hip_check(hipGetLastError(), who);
+}
+
+extern "C" int qv2x_assemble_bands(const uint8_t* slabs, int world, int64_t slab_bytes, int frames, int cout, int h, int w, int wire,
+                                   const float* da, const float* za, float* out, void* stream) {
+    using namespace qv2x;
+    const char* who = "qv2x_assemble_bands";
+    if (!slabs || !out) return fail(QV2X_EINVAL, "%s: null pointer", who);
+    if (wire != QV2X_WIRE_F32 && wire != QV2X_WIRE_U8) return fail(QV2X_EINVAL, "%s: wire %d (QV2X_WIRE_F32 or QV2X_WIRE_U8)", who, wire);
+    if (wire == QV2X_WIRE_U8 && (!da || !za)) return fail(QV2X_EINVAL, "%s: the u8 wire needs da and za", who);
+    if (world < 1 || frames < 1 || cout < 1 || h < 1 || w < 1 || (long long)h * w > 0x7fffffffLL || (long long)world * frames * cout > 65535)
+        return fail(QV2X_EINVAL, "%s: world=%d frames=%d cout=%d h=%d w=%d (world * frames * cout <= 65535)", who, world, frames, cout, h, w);
+    const long long cap = (long long)((h + world - 1) / world) * w, need = (long long)frames * cout * cap * (wire == QV2X_WIRE_U8 ? 1 : 4);
+    if (slab_bytes < need || slab_bytes % 16) return fail(QV2X_EINVAL, "%s: slab_bytes %lld (>= %lld, a multiple of 16)", who, (long long)slab_bytes, need);
+    if (((uintptr_t)slabs & 15) || ((uintptr_t)out & 15)) return fail(QV2X_EALIGN, "%s: slabs and out must be 16-byte aligned", who);
+    const int planes = frames * cout;
+    const long long quads = (cap + 3) / 4;
+    const dim3 grid((unsigned)((quads + 255) / 256 < 64 ? (quads + 255) / 256 : 64), (unsigned)(world * planes));
+    if (wire == QV2X_WIRE_U8) assemble_bands_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(slabs, slab_bytes, world, planes, cout, h, w, da, za, out);
+    else assemble_bands_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(slabs, slab_bytes, world, planes, cout, h, w, da, za, out);
+    return hip_check(hipGetLastError(), who);
 }
 
 extern "C" int qv2x_decode_heads_f32(const uint8_t* codes, int R, int hw, int levels, int kc, const float* lut, const float* lut_bias,

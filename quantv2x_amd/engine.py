@@ -254,6 +254,7 @@ class _Heads:
         self.da = _dev(np.concatenate(das + [np.full(pad, -1.0, np.float32)]), dev)
         self.za = _dev(np.concatenate(zas + [np.zeros(pad, np.float32)]), dev)
         self._w_np, self._b_np = np.concatenate(ws).astype(np.float64), np.concatenate(bs).astype(np.float64)
+        self.da_np = np.ascontiguousarray(np.concatenate(das))         # host copy: which channels have an output quantizer (the u8 band wire)
         self.lut_tables = None
 
     def collapse_over_decode(self, lut: np.ndarray, lut_bias: np.ndarray, dev):
@@ -353,6 +354,8 @@ class DeployedModel(nn.Module):
     fuse_heads_max_agents = 4           # (with three code planes: the batched form needs them; otherwise scenes of one agent -- _one_launch_agents)
     # scenes of ONE agent: every head by table look-up on the agent's own codes (qv2x_table_heads_f32; see __init__)
     single_agent_tables = True
+    band_one_launch = None              # the band path's form: None = by the agent count (as _post_form); True / False force it (tests, tools/bench_band_post.py)
+    _band_rows = None
     table_heads = None                                                   # (engines that build their own heads -- the fp32 ones -- keep the general path)
 
     def __init__(self, state: Dict[str, np.ndarray], device="cuda", emit_single_preds: Optional[bool] = None):
@@ -889,6 +892,77 @@ class DeployedModel(nn.Module):
         form = self._post_form(lens, None, own_codes is not None and frame_stride == self.fh * self.fw)
         return self._post(form, L.ptr(gathered), agent_stride, level_stride, None, pairwise, [f * frame_stride for f in range(frames)], lens, ego,
                           own_codes, frames)
+
+    # ---- the ego's post stage in row bands (dist.py: shard_post) -----------------------------------------------------------------
+    def band_shape(self):
+        """(cout, H, W) of the stacked cls | reg | dir predictions a band is cut from"""
+        self._workspace(1)
+        return self.heads.cout, self.fh, self.fw
+
+    def head_wire_supported(self, wire: str) -> bool:
+        """Can a band's predictions travel as ``wire``?  "f32" always; "u8" (the output quantizer's codes) iff every channel of the heads
+        has an output quantizer."""
+        if wire not in L.WIRES:
+            raise ValueError(f"wire: one of {sorted(L.WIRES)}, got {wire!r}")
+        return wire == "f32" or bool((self.heads.da_np > 0).all())
+
+    def fuse_frames_and_heads_band(self, gathered: torch.Tensor, agent_stride: int, level_stride: int, frame_stride: int, pairwise: torch.Tensor,
+                                   n_agents: int, ego: int, frames: int, y0: int, y1: int, out_slab: torch.Tensor, wire: str = "f32"):
+        """a7-a11 of ``fuse_frames_and_heads`` for the rows ``[y0, y1)`` of the ego's map only, straight into ``out_slab`` (u8 bytes): the
+        compact band ``[frames][cout][(y1 - y0) * W]`` as fp32 values (``wire="f32"``) or output-quantizer codes (``"u8"``).  Bit for bit the
+        same cells as the whole-map call.  Never the single-agent table look-up (another fp32 association) and no ``*_single`` heads (they are
+        not a function of the ego's map: ``single_preds``).  One launch per 64 frames up to ``_one_launch_agents()`` agents, else the fused
+        rows of the band (a buffer kept per shape: nothing is allocated once warm) and the heads on them -- the whole-map selector's rule."""
+        if not self.head_wire_supported(wire):
+            raise L.Qv2xError("band wire 'u8': a head without an output quantizer has no codes to send")
+        hd, n_cells, esz = self.heads, (y1 - y0) * self.fw, (1 if wire == "u8" else 4)
+        if not 0 <= y0 <= y1 <= self.fh:
+            raise ValueError(f"band rows [{y0}, {y1}) outside the map's {self.fh} rows")
+        if out_slab.dtype != torch.uint8 or out_slab.numel() < frames * hd.cout * n_cells * esz:
+            raise ValueError("out_slab: u8, at least frames * cout * band cells * element size bytes")
+        if n_cells == 0:
+            return
+        one_launch = self.band_one_launch
+        if one_launch is None:
+            one_launch = frames * n_cells // 32 >= self.fuse_heads_min_tiles and n_agents <= self._one_launch_agents()
+        rows = None
+        if not one_launch:
+            key = (frames, n_cells)
+            if self._band_rows is None or self._band_rows[0] != key:
+                self._band_rows = (key, torch.empty((frames, n_cells, 256), dtype=torch.float32, device=self.dev))
+            rows = self._band_rows[1]
+        lut = L.ptr(self.lut) if self.has_codebook else None
+        lb = L.ptr(self.lut_bias) if self.has_codebook else None
+        base, st = out_slab.data_ptr(), L.current_stream()
+        for s0 in range(0, frames, 64):
+            s1 = min(frames, s0 + 64)
+            d = self._fuse_desc(agent_stride, level_stride, pairwise[s0], n_agents, ego)
+            offs = (C.c_int64 * (s1 - s0))(*[f * frame_stride for f in range(s0, s1)])
+            cnts = (C.c_int32 * (s1 - s0))(*([n_agents] * (s1 - s0)))
+            out = C.c_void_p(base + s0 * hd.cout * n_cells * esz)
+            if one_launch:
+                L.check(self.lib.qv2x_fuse_heads_band(C.byref(d), s1 - s0, offs, cnts, L.ptr(gathered), lut, lb, None, L.ptr(pairwise[s0]),
+                                                      y0 * self.fw, n_cells, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias), L.ptr(hd.da),
+                                                      L.ptr(hd.za), L.WIRES[wire], L.ptr(hd.da_np), out, None, st), "qv2x_fuse_heads_band")
+            else:
+                L.check(self.lib.qv2x_fuse_att_band_f32(C.byref(d), s1 - s0, offs, cnts, L.ptr(gathered), lut, lb, None, L.ptr(pairwise[s0]),
+                                                        y0 * self.fw, n_cells, L.ptr(rows[s0]), st), "qv2x_fuse_att_band_f32")
+                L.check(self.lib.qv2x_heads_band(L.ptr(rows[s0]), s1 - s0, n_cells, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias),
+                                                 L.ptr(hd.da), L.ptr(hd.za), L.WIRES[wire], L.ptr(hd.da_np), out, st), "qv2x_heads_band")
+
+    def assemble_bands(self, gathered_slabs: torch.Tensor, world: int, frames: int, wire: str, out: torch.Tensor):
+        """The gathered band slabs u8 ``[world, slab_bytes]`` -> ``out`` f32 ``[frames, cout, H, W]`` in one launch (qv2x_assemble_bands)."""
+        hd = self.heads
+        L.check(self.lib.qv2x_assemble_bands(L.ptr(gathered_slabs), world, gathered_slabs.shape[1], frames, hd.cout, self.fh, self.fw, L.WIRES[wire],
+                                             L.ptr(hd.da), L.ptr(hd.za), L.ptr(out), L.current_stream()), "qv2x_assemble_bands")
+
+    def band_output(self, preds: torch.Tensor, own_codes: Optional[torch.Tensor], frames: int) -> dict:
+        """The model's output dict from the assembled predictions ``[frames, cout, H, W]``, plus the ``*_single`` heads of this rank's own
+        agent on ``own_codes`` (u8 [levels, frames, H*W]) -- the keys of ``fuse_frames_and_heads``."""
+        out = split_heads(preds, self.heads.splits)
+        if own_codes is not None:
+            out.update(self.single_preds(own_codes, frames))
+        return out
 
     def encode_agents(self, inputs: dict, n_agents: int, taps: Optional[dict] = None):
         """a1-a6 for ``n_agents`` agents.  Returns codes u8 [levels, n, H*W] (or the i8 shrinker output without a codebook)."""

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libqv2x.so")
 MAX_GROUPS = 4
-ABI_VERSION = 7             # include/qv2x.h: QV2X_ABI_VERSION (the structs below mirror that header)
+ABI_VERSION = 8             # include/qv2x.h: QV2X_ABI_VERSION (the structs below mirror that header)
 
 SYMBOLS = [
     "qv2x_last_error", "qv2x_version", "qv2x_fill_i8", "qv2x_pfn_scatter_i8", "qv2x_pfn_unscatter_i8", "qv2x_conv3x3_i8",
@@ -26,7 +26,9 @@ SYMBOLS = [
     "qv2x_add_relu_f32", "qv2x_occ_sigmoid_f32", "qv2x_pyramid_weighted_fuse_f32p", "qv2x_bottleneck_i8",
     "qv2x_comm_unique_id", "qv2x_comm_init", "qv2x_comm_destroy", "qv2x_allgather_codes", "qv2x_pairwise_from_poses_f64", "qv2x_pairwise_from_poses_batch_f64",
     "qv2x_codebook_encode_collapsed_f32", "qv2x_codebook_encode_candidates_i8", "qv2x_codebook_encode_candidates_seg_i8", "qv2x_codebook_encode_listed_f32", "qv2x_mean_vfe_f32", "qv2x_sp_index_scatter", "qv2x_sp_out_sites_workspace_bytes", "qv2x_sp_out_sites", "qv2x_sp_rulebook", "qv2x_sp_conv_f32in", "qv2x_sp_conv_i8", "qv2x_sp_to_bev_i8",
+    "qv2x_fuse_att_band_f32", "qv2x_heads_band", "qv2x_fuse_heads_band", "qv2x_assemble_bands",
 ]
+WIRES = {"f32": 0, "u8": 1}     # QV2X_WIRE_F32, QV2X_WIRE_U8
 COMM_ID_BYTES = 128
 
 
@@ -213,6 +215,12 @@ def load() -> C.CDLL:
     lib.qv2x_allgather_codes.argtypes = [vp, vp, vp, C.c_int64, vp]
     lib.qv2x_pairwise_from_poses_f64.argtypes = [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, vp]
     lib.qv2x_pairwise_from_poses_batch_f64.argtypes = [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int, vp, vp]
+    lib.qv2x_fuse_att_band_f32.argtypes = [C.POINTER(FuseDesc), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), vp, vp, vp, vp, vp,
+                                           C.c_int64, C.c_int64, vp, vp]
+    lib.qv2x_heads_band.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    lib.qv2x_fuse_heads_band.argtypes = [C.POINTER(FuseDesc), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), vp, vp, vp, vp, vp,
+                                         C.c_int64, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.qv2x_assemble_bands.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     for s in SYMBOLS:
         if s not in ("qv2x_last_error", "qv2x_codebook_level_floats", "qv2x_codebook64_level_floats", "qv2x_voxelize_workspace_bytes", "qv2x_postprocess_workspace_bytes",
                      "qv2x_postprocess_late_workspace_bytes", "qv2x_sp_out_sites_workspace_bytes"):
