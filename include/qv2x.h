@@ -247,7 +247,7 @@ int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* desc /* host */, con
 
 /* Stage 1 for SEGMENTED and 256-entry codebooks: seg_num (desc->segs) 1 | 2, dict_size (desc->kc) a multiple of 32 up to 256 (of 64 with
  * two segments), seg_num * dict_size <= 512, up to three levels.  qv2x_codebook_encode_candidates_i8 keeps its contract (it refuses these
- * shapes); this entry has the same argument list and the same meaning, with ke = segs * kc scores per level -- the rows of the EXTENDED
+ * shapes, and its bias is packed with 128); this entry runs the same kernel, has the same argument list and the same meaning, with ke = segs * kc scores per level -- the rows of the EXTENDED
  * codebook, segment s in rows s * kc .. -- and an argmin, a (best, second) gap and a code plane PER SEGMENT:
  *   g_limbs  i8  [levels][ke/32][3][8][64][16]: as above, score tile t of a level = scores 32 t .. of its ke
  *   bias_packed f64 [levels*ke] = 256 * (rint(g / h) + (128 - zx) * rowsum(G_int)) + k,  k = the index INSIDE the segment (8 bits);

@@ -38,11 +38,12 @@ Measured on the bench's model: tau = 0.13 / 0.28 / 0.48 at levels 0 / 1 / 2 for 
 (the propagated part is ~1000x what the chain really loses -- worst-case rounding -- but the gaps are O(1), so it is affordable; tau as a
 whole is ~15x the largest gap difference measured).
 
-Segmented codebooks (seg_num m = 2) and 256 codes per segment (``segs`` below; csrc/codebook_encode_cand_seg.hip): the state holds the
-EXTENDED codebook [m kc][256], the collapsed form is the same with one argmin, one gap and one code plane PER SEGMENT, and level l adds
-m l table rows (one per segment of every earlier level) to a score.  ``encode_error_bound`` states what changes in the bound,
-``candidate_tables`` the integer ranges (packed score 256 S + k); tests/test_encode_two_stage_seg_cpu.py pins both.  Measured on the golden
-rows: 19.7 % of the cells listed at (2, 256), 9.4 % at (1, 256).
+Segmented codebooks (seg_num m = 2) and 256 codes per segment (``segs`` below; the same kernel, csrc/codebook_encode_cand.hip, through its
+second entry): the state holds the EXTENDED codebook [m kc][256], the collapsed form is the same with one argmin, one gap and one code
+plane PER SEGMENT, and level l adds m l table rows (one per segment of every earlier level) to a score.  ``encode_error_bound`` states what
+changes in the bound, ``candidate_tables`` the integer ranges (packed score 256 S + k; ``pack_factor`` and ``CANDIDATE_ENTRY`` say which
+entry takes which); tests/test_encode_two_stage_seg_cpu.py pins both.  Measured on the golden rows: 19.7 % of the cells listed at
+(2, 256), 9.4 % at (1, 256).
 
 ``tests/test_encode_two_stage_cpu.py`` pins the theory on the CPU: the numpy emulation of stage 1 (``candidate_emulate``) against the oracle
 on the reference's golden rows and on synthetic ones -- every accepted cell equal at every level, flagged fraction reported -- and, on the
@@ -155,8 +156,12 @@ def encode_error_bound(state: Dict[str, np.ndarray], levels: int, delta: float, 
 
 
 def pack_factor(segs: int, kc: int) -> int:
-    """the packed score is ``P S + k``: 128 where the index has seven bits (the first candidate kernel), 256 in the segment kernel"""
+    """the packed score is ``P S + k``: 128 where the index has seven bits and there is one segment, else 256"""
     return 128 if segs == 1 and kc <= 128 else 256
+
+
+# the stage-1 entry that takes bias packed with P (include/qv2x.h): the same kernel, instantiated for its P
+CANDIDATE_ENTRY = {128: "qv2x_codebook_encode_candidates_i8", 256: "qv2x_codebook_encode_candidates_seg_i8"}
 
 
 def candidate_tables(state: Dict[str, np.ndarray], levels: int, in_delta: float, in_zx: int, segs: int = 1) -> Dict[str, np.ndarray]:

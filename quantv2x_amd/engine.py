@@ -823,7 +823,7 @@ class DeployedModel(nn.Module):
         try:
             t = candidate_tables(self.state, self.enc_levels, float(self.shrink1.out_q[0]), int(self.shrink1.out_q[1]), self.segs)
             k = np.arange(t["bias"].shape[0], dtype=np.int64) % self.kc               # the index inside the segment
-            pf = int(t["pack"])                                          # 128 (the first candidate kernel) | 256 (the segment kernel)
+            pf = int(t["pack"])                                          # 128 | 256: encode_two_stage.pack_factor, the entry's in candidate_entry
             packed = (pf * t["bias"] + k).astype(np.float64)
             if not np.array_equal(packed.astype(np.int64), pf * t["bias"] + k):
                 raise ValueError("two-stage encode: packed scores not exact in float64")                  # (below 2^53 by construction)
@@ -832,12 +832,17 @@ class DeployedModel(nn.Module):
         except Exception as e:                                          # whatever the host algebra raises (LinAlgError, FloatingPointError, ...)
             self.encode_mode, self.two_stage_refused = "exact", str(e) or type(e).__name__
 
+    def candidate_entry(self) -> str:
+        """the stage-1 entry for this codebook: the one that takes bias packed with ``encode_two_stage.pack_factor`` (128: seg_num 1,
+        dict_size <= 128; 256: the rest), which is what ``_build_two_stage`` packed"""
+        from .encode_two_stage import CANDIDATE_ENTRY, pack_factor
+        return CANDIDATE_ENTRY[pack_factor(self.segs, self.kc)]
+
     def _encode_two_stage(self, d, b, codes):
-        """a6 as two launches (encode_two_stage.py): qv2x_codebook_encode_candidates_i8 (seg_num 1, dict_size <= 128) or
-        qv2x_codebook_encode_candidates_seg_i8 (two segments, 256 codes) decides every cell it can PROVE, the listed rest goes through the
-        reference-order kernel (qv2x_codebook_encode_listed_f32) -- identical indices, a fraction of the fp32 work."""
+        """a6 as two launches (encode_two_stage.py): the candidate stage (``candidate_entry``) decides every cell it can PROVE, the listed
+        rest goes through the reference-order kernel (qv2x_codebook_encode_listed_f32) -- identical indices, a fraction of the fp32 work."""
         gp, bias, tab, tau, _ = self._two_stage
-        name = "qv2x_codebook_encode_candidates_i8" if self.segs == 1 and self.kc <= 128 else "qv2x_codebook_encode_candidates_seg_i8"
+        name = self.candidate_entry()
         L.check(getattr(self.lib, name)(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
                                         L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), name)
         L.check(self.lib.qv2x_codebook_encode_listed_f32(C.byref(d), L.ptr(b["s1"]), self.level_ptrs, L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]),

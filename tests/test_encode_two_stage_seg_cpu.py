@@ -90,7 +90,7 @@ def chain_f64(state, levels, m, x0, codes):
 
 
 def integer_ranges(tabs, rows_u8, cand):
-    """The largest values the segment kernel holds (csrc/codebook_encode_cand_seg.hip): analytically -- every stored byte at -128 against the
+    """The largest values the candidate kernel holds at two segments / 256 codes (csrc/codebook_encode_cand.hip): analytically -- every stored byte at -128 against the
     limbs' absolute values, ``seg_num * l`` table entries of the largest magnitude -- and as attained on the rows with stage 1's own codes."""
     gi, bias, tables = tabs["g_int"], tabs["bias"].astype(np.int64), tabs["tables"].astype(np.int64)
     m, kc, P = tabs["segs"], tabs["kc"], int(tabs["pack"])

@@ -7,7 +7,11 @@ quantv2x_amd/encode_two_stage.py, pinned on the CPU by tests/test_encode_two_sta
     other dictionary sizes, several frames, and replayed from a HIP graph on fresh input;
   * stage 1 alone equals its numpy emulation bit for bit: the candidate indices of EVERY cell and the set of listed cells (so the CPU
     proof obligations are statements about what runs here);
-  * the refine fraction is the CPU's."""
+  * the two C entries of stage 1 are ONE kernel that differs in the packing factor of the score (128 S + k | 256 S + k): the same rows
+    through both give the same codes, counters and lists;
+  * the refine fraction is the CPU's.
+
+``stage1_alone`` and ``assert_stage1_is_the_emulation`` serve tests/test_hip_encode_two_stage_seg.py (two segments, 256 codes) as well."""
 import copy
 
 import numpy as np
@@ -50,7 +54,8 @@ def run_modes(eng, n):
 
 
 def stage1_alone(eng, n):
-    """qv2x_codebook_encode_candidates_i8 by itself: (codes [levels, M], sorted list of listed cells, counters)"""
+    """the candidate entry the engine would call (``eng.candidate_entry()``) by itself: (codes [levels * segs, M], sorted listed cells,
+    counters, the three lists by first undecided level)"""
     import ctypes as C
     from quantv2x_amd import lib as L
     b = eng._workspace(n)
@@ -58,23 +63,43 @@ def stage1_alone(eng, n):
     eng.encode_codes(n)                                                  # builds the operands and the buffers
     gp, bias, tab, tau, _ = eng._two_stage
     d = L.EncodeDesc()
-    d.n, d.h, d.w, d.levels, d.kc, d.segs = n, eng.fh, eng.fw, eng.enc_levels, eng.kc, 1
+    d.n, d.h, d.w, d.levels, d.kc, d.segs = n, eng.fh, eng.fw, eng.enc_levels, eng.kc, eng.segs
     d.in_zx, d.in_delta = int(eng.shrink1.out_q[1]), float(eng.shrink1.out_q[0])
-    codes = torch.zeros((eng.levels, n * eng.fh * eng.fw), dtype=torch.uint8, device="cuda")
-    L.check(eng.lib.qv2x_codebook_encode_candidates_i8(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
-                                                       L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), "candidates")
+    m_cells = n * eng.fh * eng.fw
+    codes = torch.zeros((eng.levels, m_cells), dtype=torch.uint8, device="cuda")
+    name = eng.candidate_entry()
+    L.check(getattr(eng.lib, name)(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
+                                   L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), name)
     torch.cuda.synchronize()
     cnt = b["enc_counters"].cpu().numpy().astype(np.int64)
-    m_cells = n * eng.fh * eng.fw
-    lists = [b["enc_list"][c * m_cells:c * m_cells + cnt[1 + c]].cpu().numpy().astype(np.int64) for c in range(3)]     # by first undecided level
+    lists = [b["enc_list"][c * m_cells:c * m_cells + cnt[1 + c]].cpu().numpy().astype(np.int64) for c in range(3)]
     assert cnt[0] == sum(len(v) for v in lists)
     return codes.cpu().numpy(), np.sort(np.concatenate(lists)), cnt, lists
+
+
+def assert_stage1_is_the_emulation(eng, n, codes_u8, in_delta, in_zx):
+    """stage 1 alone = ``candidate_emulate`` bit for bit: every candidate index of every cell (a listed cell's later levels follow a
+    candidate the kernel and the emulation both computed: equal as well), the listed set, the four counters, the three lists as sets (n0,
+    n1 and the in_zx arithmetic of the kernel are visible only through the listed set).  Returns (listed flags, the cells first undecided
+    at each level)."""
+    from quantv2x_amd.encode_two_stage import candidate_emulate
+    levels, m = eng.enc_levels, eng.segs
+    cand, listed, cnt, lists = stage1_alone(eng, n)
+    e_cand, e_flag, e_flags, _ = candidate_emulate(codes_u8, eng._two_stage[4], float(in_delta), int(in_zx))
+    assert e_cand.shape == cand.shape == (levels * m, len(codes_u8))
+    assert np.array_equal(cand, e_cand), f"{int((cand != e_cand).sum())} candidate indices differ from the emulation"
+    assert np.array_equal(listed, np.flatnonzero(e_flag)), (len(listed), int(e_flag.sum()))
+    lvl = [e_flags[l * m:(l + 1) * m].any(0) for l in range(levels)]               # a level is undecided if any of its segments is
+    first = [lvl[l] & ~np.any(lvl[:l], axis=0) if l else lvl[0] for l in range(levels)] + [np.zeros_like(e_flag)] * (3 - levels)
+    assert cnt[0] == e_flag.sum() and list(cnt[1:4]) == [int(f.sum()) for f in first], (cnt, [int(f.sum()) for f in first])
+    for c in range(3):                                               # list c = exactly the cells first undecided at level c
+        assert np.array_equal(np.sort(lists[c]), np.flatnonzero(first[c])), c
+    return e_flag, first
 
 
 @pytest.mark.parametrize("adversarial", [False, True])
 def test_golden_rows_two_stage_equals_exact_oracle_and_reference(golden, adversarial):
     from oracle.spec import Oracle
-    from quantv2x_amd.encode_two_stage import candidate_emulate
     g = golden["codebook_full"]
     codes_u8, rows = golden_rows(g)
     base = adversarial_state(_state()) if adversarial else _state()
@@ -88,18 +113,7 @@ def test_golden_rows_two_stage_equals_exact_oracle_and_reference(golden, adversa
     if not adversarial:
         assert np.array_equal(got["two_stage"], g["codes"]) or int((got["two_stage"] != g["codes"]).sum()) == int((want != g["codes"]).sum())
     # stage 1 alone = the CPU emulation, bit for bit: every candidate index, and exactly the same cells listed
-    cand, listed, cnt, lists = stage1_alone(eng, 1)
-    t = eng._two_stage[4]
-    e_cand, e_flag, e_flags, _ = candidate_emulate(codes_u8, t, float(g["in_delta"]), int(g["in_zp"]))
-    assert np.array_equal(listed, np.flatnonzero(e_flag)), (len(listed), int(e_flag.sum()))
-    ok = ~e_flag
-    assert np.array_equal(cand[:, ok], e_cand[:, ok])
-    # (a listed cell's later levels follow a candidate the kernel and the emulation both computed: equal as well)
-    assert np.array_equal(cand, e_cand)
-    first = [e_flags[l] & ~e_flags[:l].any(0) for l in range(3)]
-    assert cnt[0] == e_flag.sum() and list(cnt[1:4]) == [int(f.sum()) for f in first]
-    for c in range(3):                                               # list c = exactly the cells first undecided at level c
-        assert np.array_equal(np.sort(lists[c]), np.flatnonzero(first[c])), c
+    assert_stage1_is_the_emulation(eng, 1, codes_u8, g["in_delta"], g["in_zp"])
     stats = eng.encode_refine_stats(1)
     print("two-stage encode on the golden rows:", stats, "adversarial" if adversarial else "")
     assert 0.01 < stats["refined_fraction"] < 0.5
@@ -244,22 +258,6 @@ def test_stage2_alone_on_constructed_lists(golden, counts):
 
 
 # ---- the hostile families of tests/_encode_families.py: the kernels held to the statements tests/test_encode_two_stage_cpu.py proves ------------
-def assert_stage1_is_the_emulation(eng, n, codes_u8, in_delta, in_zx):
-    """stage 1 alone = ``candidate_emulate`` bit for bit: every candidate index, the three lists as sets, the four counters (n0, n1 and
-    the in_zx arithmetic of the kernel are visible only through the listed set)"""
-    from quantv2x_amd.encode_two_stage import candidate_emulate
-    levels = eng.enc_levels
-    cand, listed, cnt, lists = stage1_alone(eng, n)
-    e_cand, e_flag, e_flags, _ = candidate_emulate(codes_u8, eng._two_stage[4], float(in_delta), int(in_zx))
-    assert np.array_equal(cand, e_cand), f"{int((cand != e_cand).sum())} candidate indices differ from the emulation"
-    assert np.array_equal(listed, np.flatnonzero(e_flag)), (len(listed), int(e_flag.sum()))
-    first = [e_flags[l] & ~e_flags[:l].any(0) for l in range(levels)] + [np.zeros_like(e_flag)] * (3 - levels)
-    assert cnt[0] == e_flag.sum() and list(cnt[1:4]) == [int(f.sum()) for f in first], (cnt, [int(f.sum()) for f in first])
-    for c in range(3):
-        assert np.array_equal(np.sort(lists[c]), np.flatnonzero(first[c])), c
-    return e_flag
-
-
 def _family_names():
     import _encode_families as F
     return F.FAMILY_NAMES + tuple(F.FLAG_EVERYTHING)
@@ -295,7 +293,7 @@ def test_every_family_two_stage_equals_exact_and_oracle_and_stage1_is_the_emulat
     assert np.array_equal(got["exact"], want), f"[{fam.name}] exact kernel: {int((got['exact'] != want).sum())} indices differ from the oracle"
     mism = int((got["two_stage"] != want).sum())
     assert mism == 0, f"[{fam.name}] two-stage encode: {mism} indices differ from the oracle"
-    e_flag = assert_stage1_is_the_emulation(eng, 1, rows, fam.in_delta, fam.in_zx)
+    e_flag, _ = assert_stage1_is_the_emulation(eng, 1, rows, fam.in_delta, fam.in_zx)
     stats = eng.encode_refine_stats(1)
     print(f"two-stage encode [{fam.name}]:", stats)
     assert stats["refined"] == int(e_flag.sum())
@@ -314,8 +312,8 @@ def _big_launches():
 
 @pytest.mark.parametrize("side", ["four_tiles", "two_tiles_just_below"])
 def test_candidate_kernel_both_tile_forms_at_a_large_ragged_launch(golden, side):
-    """``encode_candidates_kernel<4>`` (the bench batch's form, reached elsewhere only end to end) and ``<2>`` just below the switch, on a
-    launch whose last workgroup is partial: stage 1 == the emulation on EVERY cell, two_stage == exact."""
+    """``encode_candidates_kernel<4, 1, 128>`` (the bench batch's form, reached elsewhere only end to end) and ``<2, 1, 128>`` just below the
+    switch, on a launch whose last workgroup is partial: stage 1 == the emulation on EVERY cell, two_stage == exact."""
     import _encode_families as F
     g = golden["codebook_full"]
     codes_u8, _ = golden_rows(g)
@@ -334,6 +332,69 @@ def test_candidate_kernel_both_tile_forms_at_a_large_ragged_launch(golden, side)
     mism = int((got["two_stage"] != got["exact"]).sum())
     assert mism == 0, f"{mism} indices of {n} frames differ between the two-stage and the exact encode"
     assert_stage1_is_the_emulation(eng, n, rows, fam.in_delta, fam.in_zx)
+
+
+@pytest.fixture(scope="module", params=[128, 64])
+def one_segment_engine(request, golden):
+    """one deploy per dict_size on the ragged map -- the (1, kc) operands of ``candidate_tables`` are built once, inside it -- for both
+    launch sizes"""
+    import _encode_families as F
+    from quantv2x_amd.engine import deploy
+    kc = request.param
+    base = copy.copy(_state())
+    for l in range(3):
+        base[f"codebook/{l}/codebook"] = np.ascontiguousarray(base[f"codebook/{l}/codebook"][:kc])
+    fam = F.family("base", base, golden["codebook_full"])
+    eng = deploy(state=F.deployable(fam, (696, 200, 1)))
+    yield kc, fam, eng
+    del eng
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("side", ["one_frame", "four_tiles"])
+def test_the_packing_factor_is_the_only_difference_between_the_entries(golden, side, one_segment_engine):
+    """A (1, kc <= 128) codebook through BOTH entries on the same rows: ``encode_candidates_kernel<CT, 1, 128>`` on bias packed as 128 b + k
+    against ``<CT, 1, 256>`` on 256 b + k, CT = 2 (one frame) and CT = 4 (the frame count at the large-tile switch), three levels, a partial
+    last workgroup.  With the integer score gap D and T = ceil(t) a cell is listed iff D <= T, or D = T + 1 with the second index below the
+    first -- for either P -- so the code planes, the four counters and the three lists (as sets) are equal."""
+    import ctypes as C
+    import _encode_families as F
+    from quantv2x_amd import lib as L
+    from quantv2x_amd.encode_two_stage import CANDIDATE_ENTRY
+    kc, fam, eng = one_segment_engine
+    cus, cells, n_hi = _big_launches()
+    n = 1 if side == "one_frame" else n_hi
+    m_cells = n * cells
+    assert (m_cells >= 4 * cus * 256) == (side == "four_tiles") and m_cells % (512 if side == "four_tiles" else 256) != 0
+    b = eng._workspace(n)
+    assert (eng.fh, eng.fw, eng.segs, eng.kc, eng.enc_levels) == (100, 348, 1, kc, 3) and eng.encode_mode == "two_stage"
+    gp, _, tab, tau, t = eng._two_stage
+    assert t["pack"] == 128 and int(np.abs(t["bias"]).max()) < 2 ** 43 - 2 ** 32      # the same grid is inside the 256 contract
+    codes_u8, _ = golden_rows(golden["codebook_full"])
+    put_rows(eng, n, F.frame_rows(codes_u8, t, fam.in_zx, m_cells))
+    eng.encode_codes(n)                                                  # (allocates the list buffers)
+    d = L.EncodeDesc()
+    d.n, d.h, d.w, d.levels, d.kc, d.segs = n, eng.fh, eng.fw, 3, kc, 1
+    d.in_zx, d.in_delta = int(eng.shrink1.out_q[1]), float(eng.shrink1.out_q[0])
+    k = np.arange(3 * kc, dtype=np.int64) % kc
+    got = {}
+    for pf in (128, 256):
+        packed = pf * t["bias"] + k
+        assert np.array_equal(packed.astype(np.float64).astype(np.int64), packed)
+        bias = torch.from_numpy(packed.astype(np.float64)).cuda()
+        codes = torch.full((3, m_cells), 255, dtype=torch.uint8, device="cuda")
+        b["enc_list"].fill_(-1)
+        L.check(getattr(eng.lib, CANDIDATE_ENTRY[pf])(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
+                                                      L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), CANDIDATE_ENTRY[pf])
+        torch.cuda.synchronize()
+        cnt = b["enc_counters"].cpu().numpy().astype(np.int64)
+        lists = [np.sort(b["enc_list"][c * m_cells:c * m_cells + cnt[1 + c]].cpu().numpy().astype(np.int64)) for c in range(3)]
+        got[pf] = (codes.cpu().numpy(), cnt, lists)
+    assert int(got[128][0].max()) < kc and 0 < got[128][1][0] < m_cells and got[128][1][0] == got[128][1][1:4].sum()
+    assert np.array_equal(got[128][0], got[256][0]), f"{int((got[128][0] != got[256][0]).sum())} candidate indices differ between the entries"
+    assert np.array_equal(got[128][1][:4], got[256][1][:4]), (got[128][1], got[256][1])
+    for c in range(3):
+        assert len(np.unique(got[128][2][c])) == len(got[128][2][c]) and np.array_equal(got[128][2][c], got[256][2][c]), c
 
 
 def test_a_failing_operand_build_ends_in_the_exact_encode(golden, monkeypatch):

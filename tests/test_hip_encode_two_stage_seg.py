@@ -1,11 +1,12 @@
 """The two-stage EXACT encode for segmented and 256-entry codebooks on the GPU: ``(seg_num, dict_size)`` = (2, 256) -- six of the reference's
-ten codebook yamls -- and (1, 256).  Stage 1 is csrc/codebook_encode_cand_seg.hip (qv2x_codebook_encode_candidates_seg_i8), stage 2 the
-widened qv2x_codebook_encode_listed_f32; theory and operands: quantv2x_amd/encode_two_stage.py, pinned on the CPU by
+ten codebook yamls -- and (1, 256).  Stage 1 is the kernel of csrc/codebook_encode_cand.hip through its second entry, packed score
+256 S + k (qv2x_codebook_encode_candidates_seg_i8), stage 2 the widened qv2x_codebook_encode_listed_f32; theory and operands: quantv2x_amd/encode_two_stage.py, pinned on the CPU by
 tests/test_encode_two_stage_seg_cpu.py.  Every count here is zero: exactness has no tolerance.
 
   * the default mode of such an engine is ``"two_stage"``, and ``two_stage == exact == Oracle.encode_rows`` on all ``levels * seg_num`` planes
     of the reference's 35 200 golden rows;
-  * stage 1 alone equals ``candidate_emulate`` bit for bit: every candidate index of every cell, the listed set, the three per-level counts;
+  * stage 1 alone equals ``candidate_emulate`` bit for bit: every candidate index of every cell, the listed set, the three per-level counts
+    (``assert_stage1_is_the_emulation`` of tests/test_hip_encode_two_stage.py, on the entry the engine calls);
   * both cell-tile forms of the kernel on a ragged launch, tiny frames through the model call, replay from a HIP graph on fresh rows;
   * stage 2 alone on constructed lists; a full bench batch of 32 frames; the refusals of the new entry."""
 import copy
@@ -15,7 +16,7 @@ import pytest
 import torch
 
 from test_codebook_full_golden import golden_rows
-from test_hip_encode_two_stage import put_rows, run_modes, v2xreal_engine
+from test_hip_encode_two_stage import assert_stage1_is_the_emulation, put_rows, run_modes, v2xreal_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -29,44 +30,6 @@ def seg_state(m, k):
     if (m, k) not in _STATES:
         _STATES[(m, k)] = export_ptq_state(calibrated_plugin("tiny", dict_size=k, seg_num=m))
     return _STATES[(m, k)]
-
-
-def stage1_alone(eng, n):
-    """qv2x_codebook_encode_candidates_seg_i8 by itself: (codes [levels * segs, M], sorted listed cells, counters, the three lists)"""
-    import ctypes as C
-    from quantv2x_amd import lib as L
-    b = eng._workspace(n)
-    eng.encode_mode = "two_stage"
-    eng.encode_codes(n)                                                  # builds the operands and the buffers
-    gp, bias, tab, tau, _ = eng._two_stage
-    d = L.EncodeDesc()
-    d.n, d.h, d.w, d.levels, d.kc, d.segs = n, eng.fh, eng.fw, eng.enc_levels, eng.kc, eng.segs
-    d.in_zx, d.in_delta = int(eng.shrink1.out_q[1]), float(eng.shrink1.out_q[0])
-    m_cells = n * eng.fh * eng.fw
-    codes = torch.zeros((eng.levels, m_cells), dtype=torch.uint8, device="cuda")
-    L.check(eng.lib.qv2x_codebook_encode_candidates_seg_i8(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
-                                                           L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), "candidates_seg")
-    torch.cuda.synchronize()
-    cnt = b["enc_counters"].cpu().numpy().astype(np.int64)
-    lists = [b["enc_list"][c * m_cells:c * m_cells + cnt[1 + c]].cpu().numpy().astype(np.int64) for c in range(3)]
-    assert cnt[0] == sum(len(v) for v in lists)
-    return codes.cpu().numpy(), np.sort(np.concatenate(lists)), cnt, lists
-
-
-def assert_stage1_is_the_emulation(eng, n, codes_u8, in_delta, in_zx):
-    from quantv2x_amd.encode_two_stage import candidate_emulate
-    levels, m = eng.enc_levels, eng.segs
-    cand, listed, cnt, lists = stage1_alone(eng, n)
-    e_cand, e_flag, e_flags, _ = candidate_emulate(codes_u8, eng._two_stage[4], float(in_delta), int(in_zx))
-    assert e_cand.shape == cand.shape == (levels * m, len(codes_u8))
-    assert np.array_equal(cand, e_cand), f"{int((cand != e_cand).sum())} candidate indices differ from the emulation"
-    assert np.array_equal(listed, np.flatnonzero(e_flag)), (len(listed), int(e_flag.sum()))
-    lvl = [e_flags[l * m:(l + 1) * m].any(0) for l in range(levels)]               # a level is undecided if any of its segments is
-    first = [lvl[l] & ~np.any(lvl[:l], axis=0) if l else lvl[0] for l in range(levels)] + [np.zeros_like(e_flag)] * (3 - levels)
-    assert cnt[0] == e_flag.sum() and list(cnt[1:4]) == [int(f.sum()) for f in first], (cnt, [int(f.sum()) for f in first])
-    for c in range(3):
-        assert np.array_equal(np.sort(lists[c]), np.flatnonzero(first[c])), c
-    return e_flag, first
 
 
 @pytest.mark.parametrize("m,k", SHAPES)
@@ -122,8 +85,8 @@ def _big_launches(ct_big):
 @pytest.mark.parametrize("m,k,ct_big", [(2, 256, 3), (1, 256, 4)])
 @pytest.mark.parametrize("side", ["large_tile", "two_tiles_just_below"])
 def test_candidate_seg_kernel_both_tile_forms_at_a_ragged_launch(golden, side, m, k, ct_big):
-    """Every cell-tile form of the kernel: ``encode_candidates_seg_kernel<3, 2>`` (the bench batch's form) and ``<4, 1>`` (a batch of a
-    (1, 256) engine, eight frames or more) at the switch, ``<2, 2>`` and ``<2, 1>`` just below it, on launches whose last workgroup is
+    """Every cell-tile form of the kernel at 256 S + k: ``encode_candidates_kernel<3, 2, 256>`` (the bench batch's form) and ``<4, 1, 256>`` (a
+    batch of a (1, 256) engine, eight frames or more) at the switch, ``<2, 2, 256>`` and ``<2, 1, 256>`` just below it, on launches whose last workgroup is
     partial: stage 1 == the emulation on EVERY cell, two_stage == exact."""
     import _encode_families as F
     from quantv2x_amd.engine import deploy

@@ -34,11 +34,12 @@ def main():
     b = eng._workspace(frames)
     gp, bias, tab, tau, _ = eng._two_stage
     d = L.EncodeDesc()
-    d.n, d.h, d.w, d.levels, d.kc, d.segs = frames, eng.fh, eng.fw, eng.enc_levels, eng.kc, 1
+    d.n, d.h, d.w, d.levels, d.kc, d.segs = frames, eng.fh, eng.fw, eng.enc_levels, eng.kc, eng.segs
     d.in_zx, d.in_delta = int(eng.shrink1.out_q[1]), float(eng.shrink1.out_q[0])
     codes = b["codes"]
-    s1 = lambda: L.check(eng.lib.qv2x_codebook_encode_candidates_i8(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
-                                                                    L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), "s1")
+    cand = getattr(eng.lib, eng.candidate_entry())
+    s1 = lambda: L.check(cand(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
+                              L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), "s1")
     s2 = lambda: L.check(eng.lib.qv2x_codebook_encode_listed_f32(C.byref(d), L.ptr(b["s1"]), eng.level_ptrs, L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]),
                                                                  L.ptr(codes), L.current_stream()), "s2")
     s1(); torch.cuda.synchronize()
@@ -57,12 +58,13 @@ def by_levels():
     eng(full)
     b = eng._workspace(frames)
     gp, bias, tab, tau, t = eng._two_stage
+    cand = getattr(eng.lib, eng.candidate_entry())
     for lv in (1, 2, 3):
         d = L.EncodeDesc()
-        d.n, d.h, d.w, d.levels, d.kc, d.segs = frames, eng.fh, eng.fw, lv, eng.kc, 1
+        d.n, d.h, d.w, d.levels, d.kc, d.segs = frames, eng.fh, eng.fw, lv, eng.kc, eng.segs
         d.in_zx, d.in_delta = int(eng.shrink1.out_q[1]), float(eng.shrink1.out_q[0])
-        s1 = lambda: L.check(eng.lib.qv2x_codebook_encode_candidates_i8(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau,
-                                                                        L.ptr(b["codes"]), L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), "s1")
+        s1 = lambda: L.check(cand(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau,
+                                  L.ptr(b["codes"]), L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), "s1")
         print(f"levels {lv}: stage 1 {bench.event_time_us(s1, 20):.1f} us", flush=True)
 
 
@@ -79,7 +81,7 @@ def empty_list():
     eng(full); eng.encode_mode = "two_stage"; eng.encode_codes(frames); torch.cuda.synchronize()
     b = eng._workspace(frames)
     d = L.EncodeDesc()
-    d.n, d.h, d.w, d.levels, d.kc, d.segs = frames, eng.fh, eng.fw, eng.enc_levels, eng.kc, 1
+    d.n, d.h, d.w, d.levels, d.kc, d.segs = frames, eng.fh, eng.fw, eng.enc_levels, eng.kc, eng.segs
     d.in_zx, d.in_delta = int(eng.shrink1.out_q[1]), float(eng.shrink1.out_q[0])
     s2 = lambda: L.check(eng.lib.qv2x_codebook_encode_listed_f32(C.byref(d), L.ptr(b["s1"]), eng.level_ptrs, L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]),
                                                                  L.ptr(b["codes"]), L.current_stream()), "s2")
