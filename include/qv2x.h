@@ -39,8 +39,9 @@ const char* qv2x_last_error(void);
 /* The ABI of this header.  A caller built against another value must not pass its structs: 5 = qv2x_encode_desc grew the trailing `segs`
  * field (round 5; a caller built before it passes garbage there unless its struct was zero-initialised -- ADVICE r5); 6 = round 6:
  * qv2x_codebook_encode_candidates_i8 / qv2x_codebook_encode_listed_f32 added, no struct changed; 7 =
- * qv2x_codebook_encode_candidates_seg_i8 added and qv2x_codebook_encode_listed_f32 widened to seg_num 2 / dict_size 256, no struct changed. */
-#define QV2X_ABI_VERSION 8
+ * qv2x_codebook_encode_candidates_seg_i8 added and qv2x_codebook_encode_listed_f32 widened to seg_num 2 / dict_size 256, no struct changed;
+ * 9 = qv2x_voxelize_batch_f32 / qv2x_postprocess_batch_f32 and their workspace queries added, no struct changed. */
+#define QV2X_ABI_VERSION 9
 int qv2x_version(void);            /* == QV2X_ABI_VERSION of the library's own build */
 
 /* Fill a padded i8 BEV tensor (border AND interior) with one byte value: the per-frame canvas clear and the
@@ -62,6 +63,22 @@ int64_t qv2x_voxelize_workspace_bytes(int n_points);
 int qv2x_voxelize_f32(const float* points, int n_points, const float* lidar_range, const float* voxel_size, int agent,
                       int max_points, int max_voxels, void* workspace, int64_t workspace_bytes,
                       float* voxel_features, int32_t* voxel_coords, int32_t* voxel_num_points, int32_t* n_voxels, void* stream);
+
+/* The same for `n_sweeps` (1..64) sweeps in ONE call whose number of launches does not depend on n_sweeps (one radix sort and one
+ * exclusive sum over the concatenated points, the sweep folded into the sort key; no host loop over sweeps, no copy from host memory:
+ * the pointer table travels as a kernel argument, every clear is a kernel -- HIP-graph capturable).
+ *   points: HOST array of n_sweeps device pointers, sweep s f32 [n_points[s]][4]; n_points: HOST int32 [n_sweeps], each 0 <= n < 2^20
+ *   (an empty sweep is valid: count 0, all its rows cleared; its pointer is not read).
+ *   Sweep s owns rows [s * capacity, (s + 1) * capacity) of voxel_features f32 [n_sweeps * capacity][max_points][4], voxel_coords
+ *   i32 [..][4] and voxel_num_points i32 [..]; voxel_counts: DEVICE int32 [n_sweeps].  Those rows and voxel_counts[s] are bit for bit
+ *   what qv2x_voxelize_f32 writes for that sweep with agent = first_agent + s and max_voxels = capacity, the defined tail rows included.
+ *   QV2X_EINVAL when the bits of n_sweeps + the bits of the grid's cells + 20 exceed the 64-bit sort key.
+ *   workspace: qv2x_voxelize_batch_workspace_bytes(n_sweeps, n_points) bytes of device memory (-1: bad arguments). */
+int64_t qv2x_voxelize_batch_workspace_bytes(int n_sweeps, const int32_t* n_points /* host */);
+int qv2x_voxelize_batch_f32(const float* const* points /* host */, const int32_t* n_points /* host */, int n_sweeps,
+                            const float* lidar_range, const float* voxel_size, int first_agent, int max_points, int capacity,
+                            void* workspace, int64_t workspace_bytes, float* voxel_features, int32_t* voxel_coords,
+                            int32_t* voxel_num_points, int32_t* voxel_counts, void* stream);
 
 /* a1 + a2.  QuantPillarVFE/QuantPFNLayer + PointPillarScatter in one pass
  * (opencood/quant/quant_block.py:589-715, opencood/models/sub_modules/pillar_vfe.py:105-155,
@@ -384,6 +401,21 @@ int64_t qv2x_postprocess_workspace_bytes(const qv2x_postprocess_desc* desc /* ho
 int qv2x_postprocess_f32(const qv2x_postprocess_desc* desc /* host */, const float* cls, const float* reg, const float* dir,
                          const float* anchors, void* workspace, int64_t workspace_bytes, float* out_corners,
                          float* out_scores, int32_t* out_labels, int32_t* out_count, void* stream);
+
+/* The same for `frames` (1..64, frames * H*W*A < 2^31) independent frames in ONE call: the frame is a grid dimension of every kernel
+ * (the one-workgroup stages of the single entry run one workgroup per frame), one exclusive sum over all frames' flags; no host loop
+ * over frames, nothing copied from host memory -- HIP-graph capturable.
+ *   cls / reg / dir: frame f's maps start at base + f * <map>_frame_stride floats (dir NULL iff num_bins == 0); anchors are shared;
+ *   transforms: DEVICE f32 [frames][16], row-major 4x4 per frame (desc->transform is ignored);
+ *   out_corners f32 [frames][max_boxes][8][3], out_scores f32 [frames][max_boxes], out_labels i32 [frames][max_boxes] (may be NULL),
+ *   out_count i32 [frames] (device).  Frame f's outputs are bit for bit what qv2x_postprocess_f32 returns for its maps with
+ *   transform = transforms[f].
+ *   workspace: qv2x_postprocess_batch_workspace_bytes(desc, frames) bytes, 256-byte aligned (-1: bad descriptor or frame count). */
+int64_t qv2x_postprocess_batch_workspace_bytes(const qv2x_postprocess_desc* desc /* host */, int frames);
+int qv2x_postprocess_batch_f32(const qv2x_postprocess_desc* desc /* host */, int frames, const float* cls, int64_t cls_frame_stride,
+                               const float* reg, int64_t reg_frame_stride, const float* dir, int64_t dir_frame_stride,
+                               const float* anchors, const float* transforms /* device */, void* workspace, int64_t workspace_bytes,
+                               float* out_corners, float* out_scores, int32_t* out_labels, int32_t* out_count, void* stream);
 
 /* Late fusion (hypes_yaml/v2x_real/LiDAROnly/lidar_late_mc_fusion.yaml): the same pipeline over `ncav` (1..8) CAVs -- the loop over
  * `cav_content` of the reference's post_process (voxel_postprocessor.py:272-345, voxel_postprocessor_3heads.py:345-420): every CAV's head

@@ -49,13 +49,10 @@ struct PPArgs {
     float* out_corners; float* out_scores; int* out_labels; int* out_count;
 };
 
-__global__ void pp_score_kernel(const PPArgs p) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;          // anchor index in (cav, h, w, a) order
-    if (i >= p.na) return;
-    const int cav = i / p.na1, li = i - cav * p.na1;
+// slot i of the workspace = anchor li of the head map `cls` (one CAV: li == i)
+__device__ __forceinline__ void pp_score_body(const PPArgs& p, const int i, const int li, const float* __restrict__ cls) {
     const int a = li % p.a, cell = li / p.a;
     const size_t hw = (size_t)p.h * p.w;
-    const float* cls = p.cls[cav];
     // one score class: the anchor's logit; several (voxel_postprocessor_3heads.py:362-373): channel a * ncls + k, the score is
     // the largest class probability (first one on ties), the label its index + 1
     float s = 1.0f / (1.0f + expf(-cls[(size_t)(a * p.ncls) * hw + cell]));
@@ -71,20 +68,20 @@ __global__ void pp_score_kernel(const PPArgs p) {
     p.idx_in[i] = i;                                               // candidate c is named by idx_in[c] == c
 }
 
+__global__ void pp_score_kernel(const PPArgs p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;          // anchor index in (cav, h, w, a) order
+    if (i >= p.na) return;
+    const int cav = i / p.na1, li = i - cav * p.na1;
+    pp_score_body(p, i, li, p.cls[cav]);
+}
+
 __device__ __forceinline__ float limit_period(float v, float offset, float period) { return v - floorf(v / period + offset) * period; }
 
-__global__ void pp_decode_kernel(const PPArgs p) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p.na) return;
-    if (!p.flag[i]) return;
-    const int c = p.pos[i];                                        // candidate number, reference order
-    const int cav = i / p.na1, li = i - cav * p.na1;
+// flagged slot i = candidate c (reference order), anchor li of one CAV's maps, projected by its row-major 4x4 matrix T
+__device__ __forceinline__ void pp_decode_body(const PPArgs& p, const int i, const int c, const int li, const float* __restrict__ reg,
+                                               const float* __restrict__ dirm, const float* __restrict__ anchors, const float* __restrict__ T) {
     const int a = li % p.a, cell = li / p.a;
     const size_t hw = (size_t)p.h * p.w;
-    const float* reg = p.reg[cav];
-    const float* dirm = p.dir[cav];
-    const float* anchors = p.anchors[cav];
-    const float* T = p.t[cav];
     float d[7], an[7];
 #pragma unroll
     for (int k = 0; k < 7; ++k) { d[k] = reg[(size_t)(a * 7 + k) * hw + cell]; an[k] = anchors[(size_t)li * 7 + k]; }
@@ -130,14 +127,23 @@ __global__ void pp_decode_kernel(const PPArgs p) {
     p.key_in[c] = keep ? __builtin_bit_cast(unsigned, s) : 0u;     // positive floats order like their bit patterns
 }
 
-__global__ void pp_sel_clear_kernel(const PPArgs p) {
+__global__ void pp_decode_kernel(const PPArgs p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.na) return;
+    if (!p.flag[i]) return;
+    const int c = p.pos[i];                                        // candidate number, reference order
+    const int cav = i / p.na1, li = i - cav * p.na1;
+    pp_decode_body(p, i, c, li, p.reg[cav], p.dir[cav], p.anchors[cav], p.t[cav]);
+}
+
+__device__ __forceinline__ void pp_sel_clear_body(const PPArgs& p) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < 2 * SEL_BINS + SEL_WORDS) p.sel[i] = 0;
 }
 
 // histogram of the 12 score bits of pass PASS (0: bits 31..20 of every non-empty slot; 1: bits 19..8 of the slots whose bits 31..20 = b1)
 template <int PASS>
-__global__ __launch_bounds__(256) void pp_sel_hist_kernel(const PPArgs p) {
+__device__ __forceinline__ void pp_sel_hist_body(const PPArgs& p) {
     __shared__ int h[SEL_BINS];
     for (int t = threadIdx.x; t < SEL_BINS; t += 256) h[t] = 0;
     __syncthreads();
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(256) void pp_sel_hist_kernel(const PPArgs p) {
 
 // the bin in which the running count FROM THE TOP reaches `want` (the last non-empty bin when the slots hold fewer): one workgroup of 1024
 template <int PASS>
-__global__ __launch_bounds__(1024) void pp_sel_pick_kernel(const PPArgs p) {
+__device__ __forceinline__ void pp_sel_pick_body(const PPArgs& p) {
     __shared__ int part[1024];
     __shared__ int found[2];
     const int* g = p.sel + PASS * SEL_BINS;
@@ -190,7 +196,7 @@ __global__ __launch_bounds__(1024) void pp_sel_pick_kernel(const PPArgs p) {
     }
 }
 
-__global__ __launch_bounds__(256) void pp_sel_compact_kernel(const PPArgs p) {
+__device__ __forceinline__ void pp_sel_compact_body(const PPArgs& p) {
     __shared__ int n_here, base;
     int* sel = p.sel + 2 * SEL_BINS;
     const unsigned thr24 = (unsigned)sel[SEL_THR24];
@@ -208,7 +214,7 @@ __global__ __launch_bounds__(256) void pp_sel_compact_kernel(const PPArgs p) {
 }
 
 // the survivors in descending (score, -slot) order = the first entries of the stable descending sort; entries past them: empty
-__global__ __launch_bounds__(1024) void pp_sel_sort_kernel(const PPArgs p) {
+__device__ __forceinline__ void pp_sel_sort_body(const PPArgs& p) {
     __shared__ unsigned long long v[SEL_CAP];
     const int t = threadIdx.x;
     const int count = p.sel[2 * SEL_BINS + SEL_COUNT];
@@ -360,7 +366,7 @@ __device__ __forceinline__ double quad_area(const double (&q)[4][2]) {
 }
 
 // row i of the suppression matrix: bit j (j > i) = IoU(i, j) > threshold.  One workgroup per row, 64 threads per word.
-__global__ __launch_bounds__(256) void pp_iou_kernel(const PPArgs p) {
+__device__ __forceinline__ void pp_iou_body(const PPArgs& p) {
     const int i = blockIdx.x;
     const int n = p.topk;
     double qi[4][2];
@@ -417,7 +423,7 @@ __device__ long long g_pp_fine[8];
 // result: 177 us per frame of 1000 candidates).  Now 64 candidates at a time: lane i holds candidate 64 c + i; inside the chunk only the
 // kept ones cost a step (scalar bit scan over "not yet removed", the kept one's own-chunk word by readlane); what the chunk's kept rows
 // remove further down is one wave-wide OR per later word.  Same greedy order, same result.
-__global__ __launch_bounds__(1024) void pp_sweep_kernel(const PPArgs p) {
+__device__ __forceinline__ void pp_sweep_body(const PPArgs& p) {
     constexpr int W = TOPK_MAX / 64, WP = W + 1;
     __shared__ unsigned long long m[(TOPK_MAX + 1) * WP];
     __shared__ unsigned long long pickw[W], insidew[W];
@@ -534,6 +540,62 @@ __global__ __launch_bounds__(1024) void pp_sweep_kernel(const PPArgs p) {
     PFINE(5);
 }
 
+// ---- the kernels: every stage once for one call's PPArgs, once for frame blockIdx.y of a batch -------------------------------------------
+// A batch (qv2x_postprocess_batch_f32) is `frames` independent single-CAV frames: the same stage bodies, each workgroup on the PPArgs of
+// ITS frame -- frame 0's with every workspace / map / output pointer moved on by the frame's constant stride.  flag and pos are ONE
+// [frames][na] array each (one exclusive sum over all of them; a frame's candidate numbers = the sum minus its value at the frame's first slot).
+struct PPBatch {
+    PPArgs a;                                                      // frame 0 (cls[0], reg[0], dir[0], anchors[0]: its maps; t unused)
+    long long cls_stride, reg_stride, dir_stride;                  // floats between two frames' maps
+    size_t ws_stride;                                              // bytes between two frames' workspace slabs
+    const float* transforms;                                       // device [frames][16]
+    int max_boxes;                                                 // output rows per frame
+};
+
+__device__ __forceinline__ PPArgs pp_frame(const PPBatch& b, const int f) {
+    PPArgs p = b.a;
+    const size_t o = (size_t)f * b.ws_stride;
+    auto mv = [o](auto*& q) { q = (std::remove_reference_t<decltype(q)>)((char*)q + o); };
+    mv(p.prob); mv(p.cand_corners); mv(p.cand_score); mv(p.key_in); mv(p.key_out); mv(p.idx_in); mv(p.idx_out); mv(p.mask);
+    mv(p.sel); mv(p.cand); mv(p.label); mv(p.cand_label);
+    p.flag += (size_t)f * p.na; p.pos += (size_t)f * p.na;
+    p.out_corners += (size_t)f * b.max_boxes * 24; p.out_scores += (size_t)f * b.max_boxes; p.out_count += f;
+    if (p.out_labels) p.out_labels += (size_t)f * b.max_boxes;
+    return p;
+}
+
+#define PP_STAGE(name, bounds)                                                                                          \
+    __global__ __launch_bounds__(bounds) void name##_kernel(const PPArgs p) { name##_body(p); }                       \
+    __global__ __launch_bounds__(bounds) void name##_batch_kernel(const PPBatch b) { name##_body(pp_frame(b, blockIdx.y)); }
+#define PP_STAGE_PASS(name, bounds)                                                                                     \
+    template <int PASS> __global__ __launch_bounds__(bounds) void name##_kernel(const PPArgs p) { name##_body<PASS>(p); } \
+    template <int PASS> __global__ __launch_bounds__(bounds) void name##_batch_kernel(const PPBatch b) { name##_body<PASS>(pp_frame(b, blockIdx.y)); }
+PP_STAGE(pp_sel_clear, 256)
+PP_STAGE_PASS(pp_sel_hist, 256)
+PP_STAGE_PASS(pp_sel_pick, 1024)
+PP_STAGE(pp_sel_compact, 256)
+PP_STAGE(pp_sel_sort, 1024)
+PP_STAGE(pp_iou, 256)
+PP_STAGE(pp_sweep, 1024)
+#undef PP_STAGE
+#undef PP_STAGE_PASS
+
+__global__ void pp_score_batch_kernel(const PPBatch b) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+    if (i >= b.a.na) return;
+    pp_score_body(pp_frame(b, f), i, i, b.a.cls[0] + (long long)f * b.cls_stride);
+}
+
+__global__ void pp_decode_batch_kernel(const PPBatch b) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+    if (i >= b.a.na) return;
+    const PPArgs p = pp_frame(b, f);
+    if (!p.flag[i]) return;
+    const int c = p.pos[i] - p.pos[0];                             // the flags of the frames before this one come off
+    pp_decode_body(p, i, c, i, b.a.reg[0] + (long long)f * b.reg_stride, b.a.dir[0] ? b.a.dir[0] + (long long)f * b.dir_stride : nullptr,
+                   b.a.anchors[0], b.transforms + (size_t)f * 16);
+}
+
 struct Layout {
     size_t prob, flag, pos, corners, score, key_in, key_out, idx_in, idx_out, mask, label, cand_label, sel, cand, cub, cub_bytes, total;
 };
@@ -569,6 +631,21 @@ int check_desc(const qv2x_postprocess_desc* d, const char* who) {
     return QV2X_OK;
 }
 
+// the descriptor's scalars and the workspace pointers of one call (a batch: of frame 0)
+void fill_args(PPArgs& p, const qv2x_postprocess_desc* d, const Layout& l, char* ws, int na, int na1) {
+    p.h = d->h; p.w = d->w; p.a = d->anchors_per_cell; p.na = na; p.na1 = na1; p.num_bins = d->num_bins;
+    p.topk = d->max_boxes < na ? d->max_boxes : na;
+    p.thr = d->score_threshold; p.nms_thr = d->nms_threshold; p.dir_offset = d->dir_offset;
+    p.ncls = d->num_classes; p.xy_only = d->range_xy_only; p.max_extent = d->max_extent; p.z_lo = d->z_min; p.z_hi = d->z_max;
+    for (int i = 0; i < 6; ++i) p.range[i] = d->range[i];
+    p.prob = (float*)(ws + l.prob); p.flag = (int*)(ws + l.flag); p.pos = (int*)(ws + l.pos);
+    p.cand_corners = (float*)(ws + l.corners); p.cand_score = (float*)(ws + l.score);
+    p.key_in = (unsigned*)(ws + l.key_in); p.key_out = (unsigned*)(ws + l.key_out);
+    p.idx_in = (int*)(ws + l.idx_in); p.idx_out = (int*)(ws + l.idx_out); p.mask = (unsigned long long*)(ws + l.mask);
+    p.label = (int*)(ws + l.label); p.cand_label = (int*)(ws + l.cand_label);
+    p.sel = (int*)(ws + l.sel); p.cand = (unsigned long long*)(ws + l.cand);
+}
+
 }  // namespace
 
 }  // namespace qv2x
@@ -593,17 +670,7 @@ static int postprocess_run(const qv2x_postprocess_desc* d, int ncav, const float
         p.cls[c] = cls[c]; p.reg[c] = reg[c]; p.dir[c] = d->num_bins > 0 ? dir[c] : nullptr; p.anchors[c] = anchors[c];
         for (int i = 0; i < 16; ++i) p.t[c][i] = transforms[c * 16 + i];
     }
-    p.h = d->h; p.w = d->w; p.a = d->anchors_per_cell; p.na = na; p.na1 = na1; p.num_bins = d->num_bins;
-    p.topk = d->max_boxes < na ? d->max_boxes : na;
-    p.thr = d->score_threshold; p.nms_thr = d->nms_threshold; p.dir_offset = d->dir_offset;
-    p.ncls = d->num_classes; p.xy_only = d->range_xy_only; p.max_extent = d->max_extent; p.z_lo = d->z_min; p.z_hi = d->z_max;
-    for (int i = 0; i < 6; ++i) p.range[i] = d->range[i];
-    p.prob = (float*)(ws + l.prob); p.flag = (int*)(ws + l.flag); p.pos = (int*)(ws + l.pos);
-    p.cand_corners = (float*)(ws + l.corners); p.cand_score = (float*)(ws + l.score);
-    p.key_in = (unsigned*)(ws + l.key_in); p.key_out = (unsigned*)(ws + l.key_out);
-    p.idx_in = (int*)(ws + l.idx_in); p.idx_out = (int*)(ws + l.idx_out); p.mask = (unsigned long long*)(ws + l.mask);
-    p.label = (int*)(ws + l.label); p.cand_label = (int*)(ws + l.cand_label);
-    p.sel = (int*)(ws + l.sel); p.cand = (unsigned long long*)(ws + l.cand);
+    fill_args(p, d, l, ws, na, na1);
     p.out_corners = out_corners; p.out_scores = out_scores; p.out_labels = out_labels; p.out_count = out_count;
     hipStream_t st = (hipStream_t)stream;
     const int blocks = (na + 255) / 256;
@@ -652,6 +719,88 @@ extern "C" int qv2x_postprocess_late_f32(const qv2x_postprocess_desc* d, int nca
                                          int32_t* out_count, void* stream) {
     return postprocess_run(d, ncav, cls, reg, dir, anchors, transforms, workspace, workspace_bytes, out_corners, out_scores, out_labels,
                            out_count, stream, "qv2x_postprocess_late_f32");
+}
+
+// ---- a batch of frames in one call --------------------------------------------------------------------------------------------------------
+namespace qv2x {
+namespace {
+
+struct BatchLayout { Layout one; size_t flag, pos, cub, cub_bytes, total; };
+
+BatchLayout batch_layout(int na, int frames) {
+    BatchLayout b{};
+    b.one = layout(na);                                            // a frame's slab (its own flag / pos / scan sections stay unused)
+    size_t o = b.one.total * (size_t)frames;
+    auto take = [&](size_t bytes) { const size_t at = o; o = align256(o + bytes); return at; };
+    b.flag = take((size_t)frames * na * 4); b.pos = take((size_t)frames * na * 4);
+    size_t a = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (int*)nullptr, (int*)nullptr, frames * na);
+    b.cub_bytes = a;
+    b.cub = take(a);
+    b.total = o;
+    return b;
+}
+
+constexpr int MAX_FRAMES = 64;
+
+int check_batch(const qv2x_postprocess_desc* d, int frames, const char* who) {
+    if (int rc = check_desc(d, who)) return rc;
+    if (frames < 1 || frames > MAX_FRAMES) return fail(QV2X_EINVAL, "%s: 1..%d frames", who, MAX_FRAMES);
+    const long long na = (long long)d->h * d->w * d->anchors_per_cell;
+    if (na > (1ll << 20)) return fail(QV2X_EINVAL, "%s: %lld anchors per frame; the top-k selection indexes 2^20", who, na);
+    if (na * frames >= (1ll << 31)) return fail(QV2X_EINVAL, "%s: frames * anchors must stay below 2^31", who);
+    return QV2X_OK;
+}
+
+}  // namespace
+}  // namespace qv2x
+
+extern "C" int64_t qv2x_postprocess_batch_workspace_bytes(const qv2x_postprocess_desc* d, int frames) {
+    using namespace qv2x;
+    if (check_batch(d, frames, "qv2x_postprocess_batch_workspace_bytes")) return -1;
+    return (int64_t)batch_layout(d->h * d->w * d->anchors_per_cell, frames).total;
+}
+
+extern "C" int qv2x_postprocess_batch_f32(const qv2x_postprocess_desc* d, int frames, const float* cls, int64_t cls_frame_stride,
+                                          const float* reg, int64_t reg_frame_stride, const float* dir, int64_t dir_frame_stride,
+                                          const float* anchors, const float* transforms, void* workspace, int64_t workspace_bytes,
+                                          float* out_corners, float* out_scores, int32_t* out_labels, int32_t* out_count, void* stream) {
+    using namespace qv2x;
+    const char* who = "qv2x_postprocess_batch_f32";
+    if (int rc = check_batch(d, frames, who)) return rc;
+    if (!cls || !reg || !anchors || !transforms || !workspace || !out_corners || !out_scores || !out_count) return fail(QV2X_EINVAL, "%s: null pointer", who);
+    if (d->num_bins > 0 && !dir) return fail(QV2X_EINVAL, "%s: num_bins > 0 needs the direction map", who);
+    if (cls_frame_stride < 0 || reg_frame_stride < 0 || dir_frame_stride < 0) return fail(QV2X_EINVAL, "%s: negative frame stride", who);
+    const int na = d->h * d->w * d->anchors_per_cell;
+    const BatchLayout bl = batch_layout(na, frames);
+    if (workspace_bytes < (int64_t)bl.total) return fail(QV2X_EINVAL, "%s: workspace of %lld bytes, need %lld", who, (long long)workspace_bytes, (long long)bl.total);
+    if ((uintptr_t)workspace & 255) return fail(QV2X_EALIGN, "%s: workspace must be 256-byte aligned", who);
+    char* ws = (char*)workspace;
+    PPBatch b{};
+    PPArgs& p = b.a;
+    fill_args(p, d, bl.one, ws, na, na);
+    p.flag = (int*)(ws + bl.flag); p.pos = (int*)(ws + bl.pos);
+    p.cls[0] = cls; p.reg[0] = reg; p.dir[0] = d->num_bins > 0 ? dir : nullptr; p.anchors[0] = anchors;
+    p.out_corners = out_corners; p.out_scores = out_scores; p.out_labels = out_labels; p.out_count = out_count;
+    b.cls_stride = cls_frame_stride; b.reg_stride = reg_frame_stride; b.dir_stride = dir_frame_stride;
+    b.ws_stride = bl.one.total; b.transforms = transforms; b.max_boxes = d->max_boxes;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((na + 255) / 256), F = (unsigned)frames;
+    pp_score_batch_kernel<<<dim3(blocks, F), 256, 0, st>>>(b);
+    pp_sel_clear_batch_kernel<<<dim3((2 * SEL_BINS + SEL_WORDS + 255) / 256, F), 256, 0, st>>>(b);
+    size_t tb = bl.cub_bytes;
+    if (int rc = hip_check(hipcub::DeviceScan::ExclusiveSum(ws + bl.cub, tb, p.flag, p.pos, frames * na, st), "postprocess batch scan")) return rc;
+    pp_decode_batch_kernel<<<dim3(blocks, F), 256, 0, st>>>(b);
+    const unsigned hblocks = blocks < 64 ? blocks : 64;
+    pp_sel_hist_batch_kernel<0><<<dim3(hblocks, F), 256, 0, st>>>(b);
+    pp_sel_pick_batch_kernel<0><<<dim3(1, F), 1024, 0, st>>>(b);
+    pp_sel_hist_batch_kernel<1><<<dim3(hblocks, F), 256, 0, st>>>(b);
+    pp_sel_pick_batch_kernel<1><<<dim3(1, F), 1024, 0, st>>>(b);
+    pp_sel_compact_batch_kernel<<<dim3(blocks, F), 256, 0, st>>>(b);
+    pp_sel_sort_batch_kernel<<<dim3(1, F), 1024, 0, st>>>(b);
+    pp_iou_batch_kernel<<<dim3((unsigned)p.topk, F), 256, 0, st>>>(b);
+    pp_sweep_batch_kernel<<<dim3(1, F), 1024, 0, st>>>(b);
+    return hip_check(hipGetLastError(), who);
 }
 
 #ifdef QV2X_PP_FINE

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libqv2x.so")
 MAX_GROUPS = 4
-ABI_VERSION = 8             # include/qv2x.h: QV2X_ABI_VERSION (the structs below mirror that header)
+ABI_VERSION = 9             # include/qv2x.h: QV2X_ABI_VERSION (the structs below mirror that header)
 
 SYMBOLS = [
     "qv2x_last_error", "qv2x_version", "qv2x_fill_i8", "qv2x_pfn_scatter_i8", "qv2x_pfn_unscatter_i8", "qv2x_conv3x3_i8",
@@ -27,6 +27,7 @@ SYMBOLS = [
     "qv2x_comm_unique_id", "qv2x_comm_init", "qv2x_comm_destroy", "qv2x_allgather_codes", "qv2x_pairwise_from_poses_f64", "qv2x_pairwise_from_poses_batch_f64",
     "qv2x_codebook_encode_collapsed_f32", "qv2x_codebook_encode_candidates_i8", "qv2x_codebook_encode_candidates_seg_i8", "qv2x_codebook_encode_listed_f32", "qv2x_mean_vfe_f32", "qv2x_sp_index_scatter", "qv2x_sp_out_sites_workspace_bytes", "qv2x_sp_out_sites", "qv2x_sp_rulebook", "qv2x_sp_conv_f32in", "qv2x_sp_conv_i8", "qv2x_sp_to_bev_i8",
     "qv2x_fuse_att_band_f32", "qv2x_heads_band", "qv2x_fuse_heads_band", "qv2x_assemble_bands",
+    "qv2x_voxelize_batch_workspace_bytes", "qv2x_voxelize_batch_f32", "qv2x_postprocess_batch_workspace_bytes", "qv2x_postprocess_batch_f32",
 ]
 WIRES = {"f32": 0, "u8": 1}     # QV2X_WIRE_F32, QV2X_WIRE_U8
 COMM_ID_BYTES = 128
@@ -180,6 +181,14 @@ def load() -> C.CDLL:
     lib.qv2x_voxelize_workspace_bytes.restype = C.c_int64
     lib.qv2x_voxelize_f32.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
                                       vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.qv2x_voxelize_batch_workspace_bytes.argtypes = [C.c_int, C.POINTER(C.c_int32)]
+    lib.qv2x_voxelize_batch_workspace_bytes.restype = C.c_int64
+    lib.qv2x_voxelize_batch_f32.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                            C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.qv2x_postprocess_batch_workspace_bytes.argtypes = [C.POINTER(PostprocessDesc), C.c_int]
+    lib.qv2x_postprocess_batch_workspace_bytes.restype = C.c_int64
+    lib.qv2x_postprocess_batch_f32.argtypes = [C.POINTER(PostprocessDesc), C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp,
+                                               vp, C.c_int64, vp, vp, vp, vp, vp]
     lib.qv2x_postprocess_workspace_bytes.argtypes = [C.POINTER(PostprocessDesc)]
     lib.qv2x_postprocess_workspace_bytes.restype = C.c_int64
     lib.qv2x_postprocess_f32.argtypes = [C.POINTER(PostprocessDesc), vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
@@ -223,7 +232,8 @@ def load() -> C.CDLL:
     lib.qv2x_assemble_bands.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     for s in SYMBOLS:
         if s not in ("qv2x_last_error", "qv2x_codebook_level_floats", "qv2x_codebook64_level_floats", "qv2x_voxelize_workspace_bytes", "qv2x_postprocess_workspace_bytes",
-                     "qv2x_postprocess_late_workspace_bytes", "qv2x_sp_out_sites_workspace_bytes"):
+                     "qv2x_postprocess_late_workspace_bytes", "qv2x_sp_out_sites_workspace_bytes", "qv2x_voxelize_batch_workspace_bytes",
+                     "qv2x_postprocess_batch_workspace_bytes"):
             getattr(lib, s).restype = C.c_int
     _lib = lib
     return lib

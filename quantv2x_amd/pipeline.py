@@ -1,0 +1,73 @@
+"""LiDAR sweeps -> boxes for a batch of single-agent frames, three calls around the model: ``qv2x_voxelize_batch_f32`` (all sweeps, one
+radix sort), the deployed engine, ``qv2x_postprocess_batch_f32`` (all frames, the frame a grid dimension).  Nothing is read back on the
+way, so the chain replays as one HIP graph.  Scenes of several agents are out of scope here (the voxelizer entry supports them through
+``first_agent``; the post-process of a fused scene is one frame)."""
+from __future__ import annotations
+
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from .plugin.data_utils.post_processor.voxel_postprocessor import gpu_post_process_batch
+from .voxelizer import GpuVoxelizer
+
+
+class PointsToBoxes:
+    def __init__(self, engine, voxelizer: GpuVoxelizer, postprocessor, capacity: int, max_boxes: int = 1000):
+        """``engine``: a deployed model (``quantv2x_amd.engine.deploy``); ``postprocessor``: the multi-class ``VoxelPostprocessor3Heads`` of
+        the model's yaml; ``capacity``: pillar rows handed on per sweep (rows past a sweep's voxels carry batch index -1)."""
+        self.engine, self.voxelizer, self.postprocessor = engine, voxelizer, postprocessor
+        self.capacity, self.max_boxes = int(capacity), int(max_boxes)
+        anchors = postprocessor.generate_anchor_box()
+        if not isinstance(anchors, tuple):
+            raise NotImplementedError("PointsToBoxes: the multi-class post-processor (VoxelPostprocessor3Heads) is the one wired up")
+        a = torch.as_tensor(np.array(anchors[0])).to(torch.float32).permute(1, 2, 0, 3, 4).contiguous()        # (H, W, class, anchor, 7)
+        self.anchors_dev, self.per_cell = a.reshape(-1, 7).to(voxelizer.dev), int(a.shape[2] * a.shape[3])
+        self._fixed = {}                                 # per frame count: what a call needs besides the sweeps, made once (no H2D copy later)
+
+    def _constants(self, frames: int):
+        c = self._fixed.get(frames)
+        if c is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("PointsToBoxes: first call with this many frames during HIP-graph capture (use capture())")
+            dev = self.voxelizer.dev
+            c = self._fixed[frames] = (torch.eye(4, dtype=torch.float64).reshape(1, 1, 1, 4, 4).repeat(frames, 5, 5, 1, 1).to(dev),
+                                       torch.ones(frames, dtype=torch.int64),
+                                       torch.eye(4, dtype=torch.float32).repeat(frames, 1, 1).to(dev).contiguous())
+        return c
+
+    def __call__(self, sweeps: Sequence[torch.Tensor], transforms: torch.Tensor = None) -> dict:
+        """One sweep (f32 [P, 4] on the device) per frame -> ``corners`` [frames, max_boxes, 8, 3], ``scores`` / ``labels``
+        [frames, max_boxes], ``counts`` i32 [frames] (frame f's boxes: the first ``counts[f]`` rows) and ``voxel_counts``, all on the
+        device.  ``transforms``: f32 [frames, 4, 4] on the device (default: identity)."""
+        frames = len(sweeps)
+        pairwise, record_len, eye = self._constants(frames)
+        pp = self.postprocessor
+        inp = self.voxelizer.fixed_batch(sweeps, self.capacity)
+        o = self.engine({"inputs_m1": inp, "agent_modality_list": ["m1"] * frames, "record_len": record_len, "pairwise_t_matrix": pairwise})
+        corners, scores, labels, counts = gpu_post_process_batch(
+            pp, o["cls_preds"], o["reg_preds"], None, self.anchors_dev, eye if transforms is None else transforms,
+            anchors_per_cell=self.per_cell, num_classes=int(o["cls_preds"].shape[1] // self.per_cell), num_bins=0, dir_offset=0.0,
+            rng=pp.gt_range, range_xy_only=True, max_extent=100.0, z_lim=(-100.0, 100.0), max_boxes=self.max_boxes)
+        return {"corners": corners, "scores": scores, "labels": labels, "counts": counts, "voxel_counts": inp["voxel_counts"]}
+
+    def capture(self, sweeps: Sequence[torch.Tensor], transforms: torch.Tensor = None):
+        """Capture one call into a HIP graph after two warm-up calls on a side stream (the pattern of ``engine.capture_forward``).  The
+        returned callable replays it on the same sweep tensors -- refresh their contents in place between replays, the point counts stay
+        -- and returns the same output dict; ``replay.graph`` is the graph."""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self(sweeps, transforms)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = self(sweeps, transforms)
+
+        def replay():
+            graph.replay()
+            return out
+        replay.graph = graph
+        return replay

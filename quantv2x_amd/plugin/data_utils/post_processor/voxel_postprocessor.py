@@ -78,6 +78,61 @@ def gpu_post_process(owner, cls, reg, dirp, anchors_dev, transformation_matrix, 
     return corners[:k], scores[:k], labels[:k]
 
 
+def _frame_maps(x, frames):
+    """f32 head maps [frames, C, H, W] with every frame's [C, H, W] block dense (the frames themselves may lie at any stride: a slice of a
+    larger tensor is taken as it is) -> (tensor, floats between two frames)"""
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    if x.shape[0] != frames:
+        raise ValueError(f"head maps {tuple(x.shape)}: {frames} frames expected")
+    c, h, w = (int(v) for v in x.shape[1:])
+    if tuple(x.stride()[1:]) != (h * w, w, 1) or (frames > 1 and x.stride(0) < c * h * w):
+        x = x.contiguous()
+    return x, (int(x.stride(0)) if frames > 1 else c * h * w)
+
+
+def gpu_post_process_batch(owner, cls, reg, dirp, anchors_dev, transformation_matrix, *, anchors_per_cell, num_classes, num_bins, dir_offset,
+                           rng, range_xy_only, max_extent, z_lim, max_boxes):
+    """``frames`` independent frames in ONE ``qv2x_postprocess_batch_f32`` call: ``cls`` / ``reg`` / ``dirp`` are ``[frames, C, H, W]`` head
+    maps (``dirp`` None without a direction head), ``anchors_dev`` the shared anchors, ``transformation_matrix`` a ``[frames, 4, 4]`` tensor
+    (taken as it is when it already is a contiguous f32 tensor on the maps' device -- what a HIP-graph capture needs: nothing is copied
+    from the host).  Nothing is read back: -> (corners [frames, max_boxes, 8, 3], scores [frames, max_boxes], labels i32
+    [frames, max_boxes], counts i32 [frames]) on the GPU; frame ``f``'s boxes are the first ``counts[f]`` rows of ``corners[f]``, bit for bit
+    what ``gpu_post_process`` returns for that frame."""
+    lib = load()
+    frames, dev = int(cls.shape[0]), cls.device
+    d = PostprocessDesc()
+    d.h, d.w, d.anchors_per_cell, d.num_bins = int(cls.shape[2]), int(cls.shape[3]), anchors_per_cell, num_bins
+    d.score_threshold = float(owner.params["target_args"]["score_threshold"])
+    d.nms_threshold = float(owner.params["nms_thresh"])
+    d.dir_offset = dir_offset
+    for i, v in enumerate(rng):
+        d.range[i] = float(v)
+    d.max_boxes, d.num_classes, d.range_xy_only = max_boxes, num_classes, int(range_xy_only)
+    d.max_extent, d.z_min, d.z_max = max_extent, z_lim[0], z_lim[1]
+    t = torch.as_tensor(transformation_matrix)
+    if tuple(t.shape) != (frames, 4, 4):
+        raise ValueError(f"transformation_matrix {tuple(t.shape)}: ({frames}, 4, 4) expected")
+    if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.to(device=dev, dtype=torch.float32).contiguous()
+    need = lib.qv2x_postprocess_batch_workspace_bytes(C.byref(d), frames)
+    if need < 0:
+        check(-1, "qv2x_postprocess_batch_workspace_bytes")
+    if owner._ws is None or owner._ws.numel() < need or owner._ws.device != dev:
+        owner._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    corners = torch.empty((frames, max_boxes, 8, 3), dtype=torch.float32, device=dev)
+    scores = torch.empty((frames, max_boxes), dtype=torch.float32, device=dev)
+    labels = torch.empty((frames, max_boxes), dtype=torch.int32, device=dev)
+    counts = torch.zeros((frames,), dtype=torch.int32, device=dev)
+    cls, cs = _frame_maps(cls, frames)
+    reg, rs = _frame_maps(reg, frames)
+    dirp, ds = _frame_maps(dirp, frames) if (dirp is not None and num_bins > 0) else (None, 0)
+    check(lib.qv2x_postprocess_batch_f32(C.byref(d), frames, ptr(cls), cs, ptr(reg), rs, ptr(dirp), ds, ptr(anchors_dev), ptr(t),
+                                         ptr(owner._ws), need, ptr(corners), ptr(scores), ptr(labels), ptr(counts), current_stream()),
+          "qv2x_postprocess_batch_f32")
+    return corners, scores, labels, counts
+
+
 class VoxelPostprocessor:
     def __init__(self, anchor_params, train):
         self.params = anchor_params

@@ -62,6 +62,28 @@ class GpuVoxelizer:
                                                L.ptr(nump[a * capacity:]), L.ptr(counts[a:]), L.current_stream()), "qv2x_voxelize_f32")
         return {"voxel_features": feats, "voxel_coords": coords, "voxel_num_points": nump, "voxel_counts": counts}
 
+    def fixed_batch(self, sweeps: Sequence[torch.Tensor], capacity: int, first_agent: int = 0) -> dict:
+        """``fixed`` from ONE ``qv2x_voxelize_batch_f32`` call (1..64 sweeps, one radix sort over all their points): the same dict, bit for
+        bit, with a launch count that does not grow with the number of sweeps.  Empty sweeps are allowed.  HIP-graph capturable under the
+        same condition: the sweeps keep their point counts (and their storage) between replays."""
+        n = len(sweeps)
+        sweeps = [p.contiguous() for p in sweeps]
+        feats = torch.empty((n * capacity, self.max_points, 4), dtype=torch.float32, device=self.dev)
+        coords = torch.empty((n * capacity, 4), dtype=torch.int32, device=self.dev)
+        nump = torch.empty((n * capacity,), dtype=torch.int32, device=self.dev)
+        counts = torch.zeros(n, dtype=torch.int32, device=self.dev)
+        npts = (C.c_int32 * n)(*[int(p.shape[0]) for p in sweeps])
+        table = (C.c_void_p * n)(*[p.data_ptr() if p.shape[0] else None for p in sweeps])
+        need = int(self.lib.qv2x_voxelize_batch_workspace_bytes(n, npts))
+        if need < 0:
+            L.check(-1, "qv2x_voxelize_batch_workspace_bytes")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        L.check(self.lib.qv2x_voxelize_batch_f32(table, npts, n, self.range, self.vsize, first_agent, self.max_points, capacity,
+                                                 L.ptr(self._ws), need, L.ptr(feats), L.ptr(coords), L.ptr(nump), L.ptr(counts),
+                                                 L.current_stream()), "qv2x_voxelize_batch_f32")
+        return {"voxel_features": feats, "voxel_coords": coords, "voxel_num_points": nump, "voxel_counts": counts}
+
     def __call__(self, sweeps: Sequence[torch.Tensor]) -> dict:
         """One sweep per agent -> ``inputs_m1``; agents are the batch index, as ``collate_batch`` does."""
         parts = [self.one(pts, a) for a, pts in enumerate(sweeps)]
