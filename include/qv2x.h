@@ -609,7 +609,10 @@ int qv2x_sp_index_scatter(const int32_t* coords, const int32_t* n_rows /* device
                           int32_t* volume, int set, void* stream);
 /* SparseConv3d's active outputs: every output position whose window holds an active input.  out_volume must be all -1 on entry and
  * holds the new rows on return; out_coords / *n_out are written, rows in raster order of (agent, z, y, x) (spconv's own order is hash
- * order; nothing downstream depends on it).  workspace: qv2x_sp_out_sites_workspace_bytes(desc) bytes of device memory. */
+ * order; nothing downstream depends on it).  workspace: qv2x_sp_out_sites_workspace_bytes(desc) bytes of device memory.
+ * Over capacity: when more than desc->cap_out positions are active, the FIRST cap_out of them in raster order are kept (rows 0 .. cap_out - 1,
+ * as if the list had been cut there), *n_out == cap_out, and the cells of the dropped positions are back at -1: out_coords holds no row at or
+ * beyond cap_out, a rulebook built on out_volume sees the dropped positions as absent, and undoing rows 0 .. *n_out - 1 leaves the volume clean. */
 int64_t qv2x_sp_out_sites_workspace_bytes(const qv2x_spconv_desc* desc /* host */);
 int qv2x_sp_out_sites(const qv2x_spconv_desc* desc /* host */, const int32_t* in_coords, const int32_t* n_in, int32_t* out_volume,
                       int32_t* out_coords, int32_t* n_out, void* workspace, int64_t workspace_bytes, void* stream);

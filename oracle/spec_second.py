@@ -108,11 +108,19 @@ class OracleSecond:
         self.n_layers = int(state["second/n_layers"])
         self.shape0 = [int(v) for v in state["second/sparse_shape"]]
 
-    def layer(self, i, x, idx, shape, forced_in=None):
-        """One sparse layer: ``x`` = fp32 means (i == 0) or uint8 codes; returns (codes u8 [N_out, C_out], out idx, out shape)."""
+    def level_of(self, i):
+        """The level layer ``i`` writes: 0 = the input's sites, every SparseConv3d up to and including ``i`` opens the next one."""
+        return sum(1 for j in range(i + 1) if not int(self.st[f"second/{j}/geom"][0]))
+
+    def layer(self, i, x, idx, shape, forced_in=None, site_caps=None):
+        """One sparse layer: ``x`` = fp32 means (i == 0) or uint8 codes; returns (codes u8 [N_out, C_out], out idx, out shape).
+        ``site_caps[l - 1]`` is the row capacity of level ``l`` (as ``DeployedSecondEncoder(site_caps=...)``): a SparseConv3d keeps the
+        first ``cap`` of its active outputs in raster order and drops the rest -- the contract of ``qv2x_sp_out_sites``."""
         st, p = self.st, f"second/{i}/"
         geom = [int(v) for v in st[p + "geom"]]
         oidx = idx if geom[0] else out_sites(idx, shape, geom)
+        if site_caps is not None and not geom[0]:
+            oidx = oidx[: int(site_caps[self.level_of(i) - 1])]
         nbr = rulebook(oidx, idx, shape, geom)
         wc = st[p + "w_code"].astype(np.int64)                        # [K, Cin, Cout]
         zw = st[p + "w_zp"].astype(np.int64)
@@ -139,8 +147,9 @@ class OracleSecond:
             acc = (T.astype(np.float32) * sc[None, :]).astype(np.float32)
         return _finish(acc, st, p), oidx, out_shape(shape, geom)
 
-    def forward(self, inputs, taps=None, batch_size=None):
-        """``inputs``: voxel_features / voxel_coords (agent, z, y, x) / voxel_num_points -> dense uint8 BEV codes ``[N, C * D, H, W]``."""
+    def forward(self, inputs, taps=None, batch_size=None, site_caps=None):
+        """``inputs``: voxel_features / voxel_coords (agent, z, y, x) / voxel_num_points -> dense uint8 BEV codes ``[N, C * D, H, W]``.
+        ``site_caps``: per level a SparseConv3d opens, the row capacity (see ``layer``)."""
         idx = inputs["voxel_coords"].astype(np.int32)
         n = int(idx[:, 0].max()) + 1 if batch_size is None else int(batch_size)
         x = mean_vfe(inputs["voxel_features"], inputs["voxel_num_points"])
@@ -148,7 +157,7 @@ class OracleSecond:
             taps["mean_vfe"] = x
         shape = self.shape0
         for i in range(self.n_layers):
-            x, idx, shape = self.layer(i, x, idx, shape)
+            x, idx, shape = self.layer(i, x, idx, shape, site_caps=site_caps)
             if taps is not None:
                 taps[f"second/{i}"] = (x, idx, list(shape))
         last = f"second/{self.n_layers - 1}/"
