@@ -58,13 +58,16 @@ int qv2x_fill_i8(int8_t* buf, int64_t bytes, int value, void* stream);
  *   voxel_num_points i32 [..]; n_voxels: DEVICE int32 = number of voxels written.  Rows past that count are left defined --
  *   coords (-1, -1, -1, -1) (an agent index qv2x_pfn_scatter_i8 drops), zero points, zero features -- so a caller may hand all
  *   max_voxels rows on without reading the count back.  Every clear is a kernel: the call is HIP-graph capturable.
- *   workspace: qv2x_voxelize_workspace_bytes(n_points) bytes of device memory */
+ *   points, voxel_features, voxel_coords and the workspace 16-byte aligned (QV2X_EALIGN); an empty sweep (n_points <= 0) is refused.
+ *   workspace: qv2x_voxelize_workspace_bytes(n_points) bytes of device memory (0 for n_points <= 0).
+ * ONE implementation serves this entry and the batched one below: this call IS the batch of one sweep (first_agent = agent,
+ * capacity = max_voxels) behind its own narrower argument contract. */
 int64_t qv2x_voxelize_workspace_bytes(int n_points);
 int qv2x_voxelize_f32(const float* points, int n_points, const float* lidar_range, const float* voxel_size, int agent,
                       int max_points, int max_voxels, void* workspace, int64_t workspace_bytes,
                       float* voxel_features, int32_t* voxel_coords, int32_t* voxel_num_points, int32_t* n_voxels, void* stream);
 
-/* The same for `n_sweeps` (1..64) sweeps in ONE call whose number of launches does not depend on n_sweeps (one radix sort and one
+/* `n_sweeps` (1..64) sweeps in ONE call whose number of launches does not depend on n_sweeps (one radix sort and one
  * exclusive sum over the concatenated points, the sweep folded into the sort key; no host loop over sweeps, no copy from host memory:
  * the pointer table travels as a kernel argument, every clear is a kernel -- HIP-graph capturable).
  *   points: HOST array of n_sweeps device pointers, sweep s f32 [n_points[s]][4]; n_points: HOST int32 [n_sweeps], each 0 <= n < 2^20
@@ -403,8 +406,10 @@ int qv2x_postprocess_f32(const qv2x_postprocess_desc* desc /* host */, const flo
                          float* out_scores, int32_t* out_labels, int32_t* out_count, void* stream);
 
 /* The same for `frames` (1..64, frames * H*W*A < 2^31) independent frames in ONE call: the frame is a grid dimension of every kernel
- * (the one-workgroup stages of the single entry run one workgroup per frame), one exclusive sum over all frames' flags; no host loop
- * over frames, nothing copied from host memory -- HIP-graph capturable.
+ * (the one-workgroup stages run one workgroup per frame), one exclusive sum over all frames' flags; no host loop over frames, nothing
+ * copied from host memory -- HIP-graph capturable.  ONE kernel set and ONE launch function serve the three post-process entries: a call
+ * is frames x maps-per-frame, 1 x 1 for qv2x_postprocess_f32, 1 x ncav for qv2x_postprocess_late_f32, frames x 1 here; only the source of
+ * the matrices differs (by value from the host there, a device array here).
  *   cls / reg / dir: frame f's maps start at base + f * <map>_frame_stride floats (dir NULL iff num_bins == 0); anchors are shared;
  *   transforms: DEVICE f32 [frames][16], row-major 4x4 per frame (desc->transform is ignored);
  *   out_corners f32 [frames][max_boxes][8][3], out_scores f32 [frames][max_boxes], out_labels i32 [frames][max_boxes] (may be NULL),

@@ -199,10 +199,10 @@ def _candidates(cls, reg, dirp, anchors, t, score_threshold, dir_offset, num_bin
 
 
 def post_process_late(cavs, lidar_range, score_threshold=0.2, nms_thresh=0.15, dir_offset=0.7853, num_bins=2, nms=True, num_classes=1,
-                      max_extent=6.0, z_lim=(-3.0, 1.0), range_xy_only=False, return_labels=False):
+                      max_extent=6.0, z_lim=(-3.0, 1.0), range_xy_only=False, return_labels=False, top=1000):
     """``cavs``: list of ``(cls, reg, dirp, anchors, t)``, one per CAV in the order of the reference's ``data_dict`` -- late fusion
     (voxel_postprocessor.py:272-345 / voxel_postprocessor_3heads.py:345-420): candidates of every CAV concatenated, then the single-CAV
-    tail (size / z filters, NMS, range mask) over the union.  -> as ``post_process``."""
+    tail (size / z filters, NMS over the ``top`` best scores, range mask) over the union.  -> as ``post_process``."""
     parts = [_candidates(c, r, d, a, t, score_threshold, dir_offset, num_bins, num_classes) for (c, r, d, a, t) in cavs]
     corners = np.concatenate([p[0] for p in parts]); scores = np.concatenate([p[1] for p in parts]); labels = np.concatenate([p[2] for p in parts])
     if corners.shape[0] == 0:
@@ -212,7 +212,7 @@ def post_process_late(cavs, lidar_range, score_threshold=0.2, nms_thresh=0.15, d
     keep = (xl <= max_extent) & (yl <= max_extent) & (yl != 0)     # remove_large_pred_bbx, quirk kept
     keep &= (corners[:, :, 2].min(1) >= z_lim[0]) & (corners[:, :, 2].max(1) <= z_lim[1])
     corners, scores, labels = corners[keep], scores[keep], labels[keep]
-    idx = nms_rotated(corners, scores, nms_thresh) if nms else np.argsort(-scores, kind="stable")
+    idx = nms_rotated(corners, scores, nms_thresh, top) if nms else np.argsort(-scores, kind="stable")
     corners, scores, labels = corners[idx], scores[idx], labels[idx]
     lo, hi = np.asarray(lidar_range[:3], F), np.asarray(lidar_range[3:], F)
     if range_xy_only:
@@ -225,12 +225,13 @@ def post_process_late(cavs, lidar_range, score_threshold=0.2, nms_thresh=0.15, d
 
 
 def post_process(cls, reg, dirp, anchors, t, lidar_range, score_threshold=0.2, nms_thresh=0.15, dir_offset=0.7853,
-                 num_bins=2, nms=True, num_classes=1, max_extent=6.0, z_lim=(-3.0, 1.0), range_xy_only=False, return_labels=False):
-    """-> (corners f32 [K, 8, 3], scores f32 [K]) in descending score order; ``nms=False`` keeps every filtered box.
+                 num_bins=2, nms=True, num_classes=1, max_extent=6.0, z_lim=(-3.0, 1.0), range_xy_only=False, return_labels=False, top=1000):
+    """-> (corners f32 [K, 8, 3], scores f32 [K]) in descending score order; ``nms=False`` keeps every filtered box, ``top`` is the
+    number of best-scoring boxes the NMS looks at (1000 in the reference; the GPU entry's ``max_boxes``).
 
     ``num_classes > 1`` is VoxelPostprocessor3Heads.post_process (voxel_postprocessor_3heads.py:318-478): ``anchors`` is
     then [H, W, A_all, 7] with the anchor sets already interleaved per cell ((h, w, class set, rotation) order, :354-358),
     the score the largest class probability, no direction fix; box_utils_mc's limits are ``max_extent=100``,
     ``z_lim=(-100, 100)``, ``range_xy_only=True`` with ``lidar_range`` = GT_RANGE."""
     return post_process_late([(cls, reg, dirp, anchors, t)], lidar_range, score_threshold, nms_thresh, dir_offset, num_bins, nms, num_classes,
-                             max_extent, z_lim, range_xy_only, return_labels)
+                             max_extent, z_lim, range_xy_only, return_labels, top)

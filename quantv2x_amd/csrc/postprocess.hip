@@ -1,6 +1,8 @@
 // f2: detection-head maps -> 3-D boxes on the GPU for the anchor heads; one CAV per call (intermediate /
 // early fusion) or several (late fusion: every CAV's candidates decoded and projected with ITS matrix, concatenated in CAV order,
-// then ONE filter / sort / NMS over the union -- the loop over `cav_content` of the reference's post_process):
+// then ONE filter / sort / NMS over the union -- the loop over `cav_content` of the reference's post_process), or a batch of independent
+// single-CAV frames.  ONE kernel set serves all three: a call is `frames` frames (blockIdx.y) of `ncav` maps each (the CAV of slot i is
+// i / na1) -- 1 x ncav for the single and late-fusion entries, frames x 1 for the batch:
 // VoxelPostprocessor.post_process (opencood/data_utils/post_processor/voxel_postprocessor.py:245-405; line numbers below)
 // and, with num_classes > 1, VoxelPostprocessor3Heads.post_process (voxel_postprocessor_3heads.py:318-478: score = largest
 // class probability + label, no direction fix, the limits of box_utils_mc.py, x-y range mask).
@@ -49,8 +51,48 @@ struct PPArgs {
     float* out_corners; float* out_scores; int* out_labels; int* out_count;
 };
 
-// slot i of the workspace = anchor li of the head map `cls` (one CAV: li == i)
-__device__ __forceinline__ void pp_score_body(const PPArgs& p, const int i, const int li, const float* __restrict__ cls) {
+// The kernel argument of every stage: frame 0's PPArgs and what moves them on to frame blockIdx.y -- every workspace / map / output pointer
+// by the frame's constant stride.  flag and pos are ONE [frames][na] array each (one exclusive sum over all of them; a frame's candidate
+// numbers = the sum minus its value at the frame's first slot).
+struct PPBatch {
+    PPArgs a;                                                      // frame 0
+    long long cls_stride, reg_stride, dir_stride;                  // floats between two frames' maps
+    size_t ws_stride;                                              // bytes between two frames' workspace slabs
+    const float* transforms;                                       // device [frames][16] (a batch), or null: a.t[cav], by value from the host
+    int max_boxes;                                                 // output rows per frame
+};
+
+__device__ __forceinline__ PPArgs pp_frame(const PPBatch& b, const int f) {
+    PPArgs p = b.a;
+    const size_t o = (size_t)f * b.ws_stride;
+    auto mv = [o](auto*& q) { q = (std::remove_reference_t<decltype(q)>)((char*)q + o); };
+    mv(p.prob); mv(p.cand_corners); mv(p.cand_score); mv(p.key_in); mv(p.key_out); mv(p.idx_in); mv(p.idx_out); mv(p.mask);
+    mv(p.sel); mv(p.cand); mv(p.label); mv(p.cand_label);
+    p.flag += (size_t)f * p.na; p.pos += (size_t)f * p.na;
+    p.out_corners += (size_t)f * b.max_boxes * 24; p.out_scores += (size_t)f * b.max_boxes; p.out_count += f;
+    if (p.out_labels) p.out_labels += (size_t)f * b.max_boxes;
+    return p;
+}
+
+// The two per-anchor stages run on a grid of (ncav x blocks of na1 anchors, frames): a workgroup never straddles two CAVs, so its CAV
+// (= slot / na1, at most MAX_CAVS - 1 scalar subtractions) and the map pointers chosen by it stay wave-uniform.  -> CAV; li = anchor inside it
+__device__ __forceinline__ int pp_cav(const int na1, int& li) {
+    const int per_cav = (na1 + 255) / 256;
+    int cav = 0, blk = blockIdx.x;
+    while (blk >= per_cav) { blk -= per_cav; ++cav; }
+    li = blk * 256 + threadIdx.x;
+    return cav;
+}
+unsigned pp_anchor_blocks(const PPArgs& p) { return (unsigned)((p.na / p.na1) * ((p.na1 + 255) / 256)); }
+
+// slot i of the frame's workspace (anchor index in (cav, h, w, a) order) = anchor li of its CAV's head map (one CAV: li == i)
+__global__ void pp_score_kernel(const PPBatch b) {
+    int li;
+    const int cav = pp_cav(b.a.na1, li), f = blockIdx.y;
+    if (li >= b.a.na1) return;
+    const int i = cav * b.a.na1 + li;
+    const PPArgs p = pp_frame(b, f);
+    const float* __restrict__ cls = b.a.cls[cav] + (long long)f * b.cls_stride;
     const int a = li % p.a, cell = li / p.a;
     const size_t hw = (size_t)p.h * p.w;
     // one score class: the anchor's logit; several (voxel_postprocessor_3heads.py:362-373): channel a * ncls + k, the score is
@@ -68,18 +110,28 @@ __device__ __forceinline__ void pp_score_body(const PPArgs& p, const int i, cons
     p.idx_in[i] = i;                                               // candidate c is named by idx_in[c] == c
 }
 
-__global__ void pp_score_kernel(const PPArgs p) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;          // anchor index in (cav, h, w, a) order
-    if (i >= p.na) return;
-    const int cav = i / p.na1, li = i - cav * p.na1;
-    pp_score_body(p, i, li, p.cls[cav]);
-}
-
 __device__ __forceinline__ float limit_period(float v, float offset, float period) { return v - floorf(v / period + offset) * period; }
 
 // flagged slot i = candidate c (reference order), anchor li of one CAV's maps, projected by its row-major 4x4 matrix T
-__device__ __forceinline__ void pp_decode_body(const PPArgs& p, const int i, const int c, const int li, const float* __restrict__ reg,
-                                               const float* __restrict__ dirm, const float* __restrict__ anchors, const float* __restrict__ T) {
+__global__ void pp_decode_kernel(const PPBatch b) {
+    int li;
+    const int cav = pp_cav(b.a.na1, li), f = blockIdx.y;
+    if (li >= b.a.na1) return;
+    const int i = cav * b.a.na1 + li;
+    const PPArgs p = pp_frame(b, f);
+    if (!p.flag[i]) return;
+    const int c = p.pos[i] - p.pos[0];                             // candidate number, reference order (the flags of the frames before this one come off)
+    const float* __restrict__ reg = b.a.reg[cav] + (long long)f * b.reg_stride;
+    const float* __restrict__ dirm = b.a.dir[cav] ? b.a.dir[cav] + (long long)f * b.dir_stride : nullptr;
+    const float* __restrict__ anchors = b.a.anchors[cav];
+    float T[12];                                                   // rows 0..2 of the matrix: the batch's device array, else the kernel argument
+    if (b.transforms) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T[k] = b.transforms[(size_t)f * 16 + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T[k] = b.a.t[cav][k];
+    }
     const int a = li % p.a, cell = li / p.a;
     const size_t hw = (size_t)p.h * p.w;
     float d[7], an[7];
@@ -127,23 +179,17 @@ __device__ __forceinline__ void pp_decode_body(const PPArgs& p, const int i, con
     p.key_in[c] = keep ? __builtin_bit_cast(unsigned, s) : 0u;     // positive floats order like their bit patterns
 }
 
-__global__ void pp_decode_kernel(const PPArgs p) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p.na) return;
-    if (!p.flag[i]) return;
-    const int c = p.pos[i];                                        // candidate number, reference order
-    const int cav = i / p.na1, li = i - cav * p.na1;
-    pp_decode_body(p, i, c, li, p.reg[cav], p.dir[cav], p.anchors[cav], p.t[cav]);
-}
-
-__device__ __forceinline__ void pp_sel_clear_body(const PPArgs& p) {
+// ---- the stages below: grid (their own x, frames), each workgroup on the PPArgs of ITS frame ------------------------------------------------
+__global__ __launch_bounds__(256) void pp_sel_clear_kernel(const PPBatch b) {
+    const PPArgs p = pp_frame(b, blockIdx.y);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < 2 * SEL_BINS + SEL_WORDS) p.sel[i] = 0;
 }
 
 // histogram of the 12 score bits of pass PASS (0: bits 31..20 of every non-empty slot; 1: bits 19..8 of the slots whose bits 31..20 = b1)
 template <int PASS>
-__device__ __forceinline__ void pp_sel_hist_body(const PPArgs& p) {
+__global__ __launch_bounds__(256) void pp_sel_hist_kernel(const PPBatch b) {
+    const PPArgs p = pp_frame(b, blockIdx.y);
     __shared__ int h[SEL_BINS];
     for (int t = threadIdx.x; t < SEL_BINS; t += 256) h[t] = 0;
     __syncthreads();
@@ -162,7 +208,8 @@ __device__ __forceinline__ void pp_sel_hist_body(const PPArgs& p) {
 
 // the bin in which the running count FROM THE TOP reaches `want` (the last non-empty bin when the slots hold fewer): one workgroup of 1024
 template <int PASS>
-__device__ __forceinline__ void pp_sel_pick_body(const PPArgs& p) {
+__global__ __launch_bounds__(1024) void pp_sel_pick_kernel(const PPBatch b) {
+    const PPArgs p = pp_frame(b, blockIdx.y);
     __shared__ int part[1024];
     __shared__ int found[2];
     const int* g = p.sel + PASS * SEL_BINS;
@@ -196,7 +243,8 @@ __device__ __forceinline__ void pp_sel_pick_body(const PPArgs& p) {
     }
 }
 
-__device__ __forceinline__ void pp_sel_compact_body(const PPArgs& p) {
+__global__ __launch_bounds__(256) void pp_sel_compact_kernel(const PPBatch b) {
+    const PPArgs p = pp_frame(b, blockIdx.y);
     __shared__ int n_here, base;
     int* sel = p.sel + 2 * SEL_BINS;
     const unsigned thr24 = (unsigned)sel[SEL_THR24];
@@ -214,6 +262,8 @@ __device__ __forceinline__ void pp_sel_compact_body(const PPArgs& p) {
 }
 
 // the survivors in descending (score, -slot) order = the first entries of the stable descending sort; entries past them: empty
+// (a body behind a one-line kernel, unlike the other stages: with the frame's PPArgs as a local of the kernel itself the compiler branched
+// around the tie path's predicated loads, 142 -> 145 us on that path)
 __device__ __forceinline__ void pp_sel_sort_body(const PPArgs& p) {
     __shared__ unsigned long long v[SEL_CAP];
     const int t = threadIdx.x;
@@ -321,6 +371,8 @@ __device__ __forceinline__ void pp_sel_sort_body(const PPArgs& p) {
     }
 }
 
+__global__ __launch_bounds__(1024) void pp_sel_sort_kernel(const PPBatch b) { pp_sel_sort_body(pp_frame(b, blockIdx.y)); }
+
 // area of the intersection of two convex quadrilaterals, Sutherland-Hodgman in fp64 (oracle/postprocess.py)
 __device__ double quad_inter_area(const double (&p)[4][2], const double (&q)[4][2]) {
     double qa = 0.0;
@@ -366,7 +418,8 @@ __device__ __forceinline__ double quad_area(const double (&q)[4][2]) {
 }
 
 // row i of the suppression matrix: bit j (j > i) = IoU(i, j) > threshold.  One workgroup per row, 64 threads per word.
-__device__ __forceinline__ void pp_iou_body(const PPArgs& p) {
+__global__ __launch_bounds__(256) void pp_iou_kernel(const PPBatch b) {
+    const PPArgs p = pp_frame(b, blockIdx.y);
     const int i = blockIdx.x;
     const int n = p.topk;
     double qi[4][2];
@@ -423,7 +476,8 @@ __device__ long long g_pp_fine[8];
 // result: 177 us per frame of 1000 candidates).  Now 64 candidates at a time: lane i holds candidate 64 c + i; inside the chunk only the
 // kept ones cost a step (scalar bit scan over "not yet removed", the kept one's own-chunk word by readlane); what the chunk's kept rows
 // remove further down is one wave-wide OR per later word.  Same greedy order, same result.
-__device__ __forceinline__ void pp_sweep_body(const PPArgs& p) {
+__global__ __launch_bounds__(1024) void pp_sweep_kernel(const PPBatch b) {
+    const PPArgs p = pp_frame(b, blockIdx.y);
     constexpr int W = TOPK_MAX / 64, WP = W + 1;
     __shared__ unsigned long long m[(TOPK_MAX + 1) * WP];
     __shared__ unsigned long long pickw[W], insidew[W];
@@ -540,62 +594,6 @@ __device__ __forceinline__ void pp_sweep_body(const PPArgs& p) {
     PFINE(5);
 }
 
-// ---- the kernels: every stage once for one call's PPArgs, once for frame blockIdx.y of a batch -------------------------------------------
-// A batch (qv2x_postprocess_batch_f32) is `frames` independent single-CAV frames: the same stage bodies, each workgroup on the PPArgs of
-// ITS frame -- frame 0's with every workspace / map / output pointer moved on by the frame's constant stride.  flag and pos are ONE
-// [frames][na] array each (one exclusive sum over all of them; a frame's candidate numbers = the sum minus its value at the frame's first slot).
-struct PPBatch {
-    PPArgs a;                                                      // frame 0 (cls[0], reg[0], dir[0], anchors[0]: its maps; t unused)
-    long long cls_stride, reg_stride, dir_stride;                  // floats between two frames' maps
-    size_t ws_stride;                                              // bytes between two frames' workspace slabs
-    const float* transforms;                                       // device [frames][16]
-    int max_boxes;                                                 // output rows per frame
-};
-
-__device__ __forceinline__ PPArgs pp_frame(const PPBatch& b, const int f) {
-    PPArgs p = b.a;
-    const size_t o = (size_t)f * b.ws_stride;
-    auto mv = [o](auto*& q) { q = (std::remove_reference_t<decltype(q)>)((char*)q + o); };
-    mv(p.prob); mv(p.cand_corners); mv(p.cand_score); mv(p.key_in); mv(p.key_out); mv(p.idx_in); mv(p.idx_out); mv(p.mask);
-    mv(p.sel); mv(p.cand); mv(p.label); mv(p.cand_label);
-    p.flag += (size_t)f * p.na; p.pos += (size_t)f * p.na;
-    p.out_corners += (size_t)f * b.max_boxes * 24; p.out_scores += (size_t)f * b.max_boxes; p.out_count += f;
-    if (p.out_labels) p.out_labels += (size_t)f * b.max_boxes;
-    return p;
-}
-
-#define PP_STAGE(name, bounds)                                                                                          \
-    __global__ __launch_bounds__(bounds) void name##_kernel(const PPArgs p) { name##_body(p); }                       \
-    __global__ __launch_bounds__(bounds) void name##_batch_kernel(const PPBatch b) { name##_body(pp_frame(b, blockIdx.y)); }
-#define PP_STAGE_PASS(name, bounds)                                                                                     \
-    template <int PASS> __global__ __launch_bounds__(bounds) void name##_kernel(const PPArgs p) { name##_body<PASS>(p); } \
-    template <int PASS> __global__ __launch_bounds__(bounds) void name##_batch_kernel(const PPBatch b) { name##_body<PASS>(pp_frame(b, blockIdx.y)); }
-PP_STAGE(pp_sel_clear, 256)
-PP_STAGE_PASS(pp_sel_hist, 256)
-PP_STAGE_PASS(pp_sel_pick, 1024)
-PP_STAGE(pp_sel_compact, 256)
-PP_STAGE(pp_sel_sort, 1024)
-PP_STAGE(pp_iou, 256)
-PP_STAGE(pp_sweep, 1024)
-#undef PP_STAGE
-#undef PP_STAGE_PASS
-
-__global__ void pp_score_batch_kernel(const PPBatch b) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
-    if (i >= b.a.na) return;
-    pp_score_body(pp_frame(b, f), i, i, b.a.cls[0] + (long long)f * b.cls_stride);
-}
-
-__global__ void pp_decode_batch_kernel(const PPBatch b) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
-    if (i >= b.a.na) return;
-    const PPArgs p = pp_frame(b, f);
-    if (!p.flag[i]) return;
-    const int c = p.pos[i] - p.pos[0];                             // the flags of the frames before this one come off
-    pp_decode_body(p, i, c, i, b.a.reg[0] + (long long)f * b.reg_stride, b.a.dir[0] ? b.a.dir[0] + (long long)f * b.dir_stride : nullptr,
-                   b.a.anchors[0], b.transforms + (size_t)f * 16);
-}
-
 struct Layout {
     size_t prob, flag, pos, corners, score, key_in, key_out, idx_in, idx_out, mask, label, cand_label, sel, cand, cub, cub_bytes, total;
 };
@@ -646,85 +644,7 @@ void fill_args(PPArgs& p, const qv2x_postprocess_desc* d, const Layout& l, char*
     p.sel = (int*)(ws + l.sel); p.cand = (unsigned long long*)(ws + l.cand);
 }
 
-}  // namespace
-
-}  // namespace qv2x
-
-static int postprocess_run(const qv2x_postprocess_desc* d, int ncav, const float* const* cls, const float* const* reg, const float* const* dir,
-                           const float* const* anchors, const float* transforms, void* workspace, int64_t workspace_bytes, float* out_corners,
-                           float* out_scores, int32_t* out_labels, int32_t* out_count, void* stream, const char* who) {
-    using namespace qv2x;
-    if (int rc = check_desc(d, who)) return rc;
-    if (ncav < 1 || ncav > MAX_CAVS) return fail(QV2X_EINVAL, "%s: 1..%d CAVs", who, MAX_CAVS);
-    if (!cls || !reg || !anchors || !transforms || !workspace || !out_corners || !out_scores || !out_count) return fail(QV2X_EINVAL, "%s: null pointer", who);
-    const int na1 = d->h * d->w * d->anchors_per_cell, na = na1 * ncav;
-    if ((long long)na1 * ncav > (1ll << 20)) return fail(QV2X_EINVAL, "%s: %lld anchors in all; the top-k selection indexes 2^20", who, (long long)na1 * ncav);
-    const Layout l = layout(na);
-    if (workspace_bytes < (int64_t)l.total) return fail(QV2X_EINVAL, "%s: workspace of %lld bytes, need %lld", who, (long long)workspace_bytes, (long long)l.total);
-    if ((uintptr_t)workspace & 255) return fail(QV2X_EALIGN, "%s: workspace must be 256-byte aligned", who);
-    char* ws = (char*)workspace;
-    PPArgs p{};
-    for (int c = 0; c < ncav; ++c) {
-        if (!cls[c] || !reg[c] || !anchors[c]) return fail(QV2X_EINVAL, "%s: null map of CAV %d", who, c);
-        if (d->num_bins > 0 && (!dir || !dir[c])) return fail(QV2X_EINVAL, "%s: num_bins > 0 needs the direction map", who);
-        p.cls[c] = cls[c]; p.reg[c] = reg[c]; p.dir[c] = d->num_bins > 0 ? dir[c] : nullptr; p.anchors[c] = anchors[c];
-        for (int i = 0; i < 16; ++i) p.t[c][i] = transforms[c * 16 + i];
-    }
-    fill_args(p, d, l, ws, na, na1);
-    p.out_corners = out_corners; p.out_scores = out_scores; p.out_labels = out_labels; p.out_count = out_count;
-    hipStream_t st = (hipStream_t)stream;
-    const int blocks = (na + 255) / 256;
-    int rc;
-    pp_score_kernel<<<blocks, 256, 0, st>>>(p);
-    pp_sel_clear_kernel<<<(2 * SEL_BINS + SEL_WORDS + 255) / 256, 256, 0, st>>>(p);
-    size_t tb = l.cub_bytes;
-    if ((rc = hip_check(hipcub::DeviceScan::ExclusiveSum(ws + l.cub, tb, p.flag, p.pos, na, st), "postprocess scan"))) return rc;
-    pp_decode_kernel<<<blocks, 256, 0, st>>>(p);
-    // the first `topk` entries of the stable descending order (see SEL_* above)
-    const int hblocks = blocks < 64 ? blocks : 64;                 // (4096 LDS bins to clear and flush per workgroup)
-    pp_sel_hist_kernel<0><<<hblocks, 256, 0, st>>>(p);
-    pp_sel_pick_kernel<0><<<1, 1024, 0, st>>>(p);
-    pp_sel_hist_kernel<1><<<hblocks, 256, 0, st>>>(p);
-    pp_sel_pick_kernel<1><<<1, 1024, 0, st>>>(p);
-    pp_sel_compact_kernel<<<blocks, 256, 0, st>>>(p);
-    pp_sel_sort_kernel<<<1, 1024, 0, st>>>(p);
-    pp_iou_kernel<<<p.topk, 256, 0, st>>>(p);
-    pp_sweep_kernel<<<1, 1024, 0, st>>>(p);
-    return hip_check(hipGetLastError(), who);
-}
-
-extern "C" int64_t qv2x_postprocess_workspace_bytes(const qv2x_postprocess_desc* d) {
-    using namespace qv2x;
-    if (check_desc(d, "qv2x_postprocess_workspace_bytes")) return -1;
-    return (int64_t)layout(d->h * d->w * d->anchors_per_cell).total;
-}
-
-extern "C" int64_t qv2x_postprocess_late_workspace_bytes(const qv2x_postprocess_desc* d, int ncav) {
-    using namespace qv2x;
-    if (check_desc(d, "qv2x_postprocess_late_workspace_bytes") || ncav < 1 || ncav > MAX_CAVS) return -1;
-    return (int64_t)layout(d->h * d->w * d->anchors_per_cell * ncav).total;
-}
-
-extern "C" int qv2x_postprocess_f32(const qv2x_postprocess_desc* d, const float* cls, const float* reg, const float* dir,
-                                    const float* anchors, void* workspace, int64_t workspace_bytes, float* out_corners,
-                                    float* out_scores, int32_t* out_labels, int32_t* out_count, void* stream) {
-    if (!d) return qv2x::fail(QV2X_EINVAL, "qv2x_postprocess_f32: null descriptor");
-    return postprocess_run(d, 1, &cls, &reg, &dir, &anchors, d->transform, workspace, workspace_bytes, out_corners, out_scores, out_labels,
-                           out_count, stream, "qv2x_postprocess_f32");
-}
-
-extern "C" int qv2x_postprocess_late_f32(const qv2x_postprocess_desc* d, int ncav, const float* const* cls, const float* const* reg,
-                                         const float* const* dir, const float* const* anchors, const float* transforms, void* workspace,
-                                         int64_t workspace_bytes, float* out_corners, float* out_scores, int32_t* out_labels,
-                                         int32_t* out_count, void* stream) {
-    return postprocess_run(d, ncav, cls, reg, dir, anchors, transforms, workspace, workspace_bytes, out_corners, out_scores, out_labels,
-                           out_count, stream, "qv2x_postprocess_late_f32");
-}
-
-// ---- a batch of frames in one call --------------------------------------------------------------------------------------------------------
-namespace qv2x {
-namespace {
-
+// a batch: the frames' slabs, then ONE flag / pos array pair and the scan's storage over all frames
 struct BatchLayout { Layout one; size_t flag, pos, cub, cub_bytes, total; };
 
 BatchLayout batch_layout(int na, int frames) {
@@ -752,8 +672,71 @@ int check_batch(const qv2x_postprocess_desc* d, int frames, const char* who) {
     return QV2X_OK;
 }
 
+// The launch sequence of every entry: `frames` frames of b.a.na slots; `scan`: hipCUB's storage for the one exclusive sum over all flags.
+int postprocess_run(const PPBatch& b, int frames, void* scan, size_t scan_bytes, void* stream, const char* who) {
+    const PPArgs& p = b.a;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((p.na + 255) / 256), F = (unsigned)frames;
+    pp_score_kernel<<<dim3(pp_anchor_blocks(p), F), 256, 0, st>>>(b);
+    pp_sel_clear_kernel<<<dim3((2 * SEL_BINS + SEL_WORDS + 255) / 256, F), 256, 0, st>>>(b);
+    if (int rc = hip_check(hipcub::DeviceScan::ExclusiveSum(scan, scan_bytes, p.flag, p.pos, frames * p.na, st), "postprocess scan")) return rc;
+    pp_decode_kernel<<<dim3(pp_anchor_blocks(p), F), 256, 0, st>>>(b);
+    // the first `topk` entries of the stable descending order (see SEL_* above)
+    const unsigned hblocks = blocks < 64 ? blocks : 64;            // (4096 LDS bins to clear and flush per workgroup)
+    pp_sel_hist_kernel<0><<<dim3(hblocks, F), 256, 0, st>>>(b);
+    pp_sel_pick_kernel<0><<<dim3(1, F), 1024, 0, st>>>(b);
+    pp_sel_hist_kernel<1><<<dim3(hblocks, F), 256, 0, st>>>(b);
+    pp_sel_pick_kernel<1><<<dim3(1, F), 1024, 0, st>>>(b);
+    pp_sel_compact_kernel<<<dim3(blocks, F), 256, 0, st>>>(b);
+    pp_sel_sort_kernel<<<dim3(1, F), 1024, 0, st>>>(b);
+    pp_iou_kernel<<<dim3((unsigned)p.topk, F), 256, 0, st>>>(b);
+    pp_sweep_kernel<<<dim3(1, F), 1024, 0, st>>>(b);
+    return hip_check(hipGetLastError(), who);
+}
+
+// the single and the late-fusion entry: ONE frame of `ncav` maps, their matrices by value in the kernel argument (no copy: these calls
+// are captured into HIP graphs)
+int postprocess_one_frame(const qv2x_postprocess_desc* d, int ncav, const float* const* cls, const float* const* reg, const float* const* dir,
+                          const float* const* anchors, const float* transforms, void* workspace, int64_t workspace_bytes, float* out_corners,
+                          float* out_scores, int32_t* out_labels, int32_t* out_count, void* stream, const char* who) {
+    if (int rc = check_desc(d, who)) return rc;
+    if (ncav < 1 || ncav > MAX_CAVS) return fail(QV2X_EINVAL, "%s: 1..%d CAVs", who, MAX_CAVS);
+    if (!cls || !reg || !anchors || !transforms || !workspace || !out_corners || !out_scores || !out_count) return fail(QV2X_EINVAL, "%s: null pointer", who);
+    const int na1 = d->h * d->w * d->anchors_per_cell, na = na1 * ncav;
+    if ((long long)na1 * ncav > (1ll << 20)) return fail(QV2X_EINVAL, "%s: %lld anchors in all; the top-k selection indexes 2^20", who, (long long)na1 * ncav);
+    const Layout l = layout(na);
+    if (workspace_bytes < (int64_t)l.total) return fail(QV2X_EINVAL, "%s: workspace of %lld bytes, need %lld", who, (long long)workspace_bytes, (long long)l.total);
+    if ((uintptr_t)workspace & 255) return fail(QV2X_EALIGN, "%s: workspace must be 256-byte aligned", who);
+    char* ws = (char*)workspace;
+    PPBatch b{};                                                   // (strides 0, transforms null: one frame)
+    PPArgs& p = b.a;
+    for (int c = 0; c < ncav; ++c) {
+        if (!cls[c] || !reg[c] || !anchors[c]) return fail(QV2X_EINVAL, "%s: null map of CAV %d", who, c);
+        if (d->num_bins > 0 && (!dir || !dir[c])) return fail(QV2X_EINVAL, "%s: num_bins > 0 needs the direction map", who);
+        p.cls[c] = cls[c]; p.reg[c] = reg[c]; p.dir[c] = d->num_bins > 0 ? dir[c] : nullptr; p.anchors[c] = anchors[c];
+        for (int i = 0; i < 16; ++i) p.t[c][i] = transforms[c * 16 + i];
+    }
+    fill_args(p, d, l, ws, na, na1);
+    p.out_corners = out_corners; p.out_scores = out_scores; p.out_labels = out_labels; p.out_count = out_count;
+    b.max_boxes = d->max_boxes;
+    return postprocess_run(b, 1, ws + l.cub, l.cub_bytes, stream, who);
+}
+
 }  // namespace
+
 }  // namespace qv2x
+
+extern "C" int64_t qv2x_postprocess_workspace_bytes(const qv2x_postprocess_desc* d) {
+    using namespace qv2x;
+    if (check_desc(d, "qv2x_postprocess_workspace_bytes")) return -1;
+    return (int64_t)layout(d->h * d->w * d->anchors_per_cell).total;
+}
+
+extern "C" int64_t qv2x_postprocess_late_workspace_bytes(const qv2x_postprocess_desc* d, int ncav) {
+    using namespace qv2x;
+    if (check_desc(d, "qv2x_postprocess_late_workspace_bytes") || ncav < 1 || ncav > MAX_CAVS) return -1;
+    return (int64_t)layout(d->h * d->w * d->anchors_per_cell * ncav).total;
+}
 
 extern "C" int64_t qv2x_postprocess_batch_workspace_bytes(const qv2x_postprocess_desc* d, int frames) {
     using namespace qv2x;
@@ -761,6 +744,23 @@ extern "C" int64_t qv2x_postprocess_batch_workspace_bytes(const qv2x_postprocess
     return (int64_t)batch_layout(d->h * d->w * d->anchors_per_cell, frames).total;
 }
 
+extern "C" int qv2x_postprocess_f32(const qv2x_postprocess_desc* d, const float* cls, const float* reg, const float* dir,
+                                    const float* anchors, void* workspace, int64_t workspace_bytes, float* out_corners,
+                                    float* out_scores, int32_t* out_labels, int32_t* out_count, void* stream) {
+    if (!d) return qv2x::fail(QV2X_EINVAL, "qv2x_postprocess_f32: null descriptor");
+    return qv2x::postprocess_one_frame(d, 1, &cls, &reg, &dir, &anchors, d->transform, workspace, workspace_bytes, out_corners, out_scores,
+                                       out_labels, out_count, stream, "qv2x_postprocess_f32");
+}
+
+extern "C" int qv2x_postprocess_late_f32(const qv2x_postprocess_desc* d, int ncav, const float* const* cls, const float* const* reg,
+                                         const float* const* dir, const float* const* anchors, const float* transforms, void* workspace,
+                                         int64_t workspace_bytes, float* out_corners, float* out_scores, int32_t* out_labels,
+                                         int32_t* out_count, void* stream) {
+    return qv2x::postprocess_one_frame(d, ncav, cls, reg, dir, anchors, transforms, workspace, workspace_bytes, out_corners, out_scores,
+                                       out_labels, out_count, stream, "qv2x_postprocess_late_f32");
+}
+
+// `frames` frames of one map each, their matrices in a device array
 extern "C" int qv2x_postprocess_batch_f32(const qv2x_postprocess_desc* d, int frames, const float* cls, int64_t cls_frame_stride,
                                           const float* reg, int64_t reg_frame_stride, const float* dir, int64_t dir_frame_stride,
                                           const float* anchors, const float* transforms, void* workspace, int64_t workspace_bytes,
@@ -784,23 +784,7 @@ extern "C" int qv2x_postprocess_batch_f32(const qv2x_postprocess_desc* d, int fr
     p.out_corners = out_corners; p.out_scores = out_scores; p.out_labels = out_labels; p.out_count = out_count;
     b.cls_stride = cls_frame_stride; b.reg_stride = reg_frame_stride; b.dir_stride = dir_frame_stride;
     b.ws_stride = bl.one.total; b.transforms = transforms; b.max_boxes = d->max_boxes;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)((na + 255) / 256), F = (unsigned)frames;
-    pp_score_batch_kernel<<<dim3(blocks, F), 256, 0, st>>>(b);
-    pp_sel_clear_batch_kernel<<<dim3((2 * SEL_BINS + SEL_WORDS + 255) / 256, F), 256, 0, st>>>(b);
-    size_t tb = bl.cub_bytes;
-    if (int rc = hip_check(hipcub::DeviceScan::ExclusiveSum(ws + bl.cub, tb, p.flag, p.pos, frames * na, st), "postprocess batch scan")) return rc;
-    pp_decode_batch_kernel<<<dim3(blocks, F), 256, 0, st>>>(b);
-    const unsigned hblocks = blocks < 64 ? blocks : 64;
-    pp_sel_hist_batch_kernel<0><<<dim3(hblocks, F), 256, 0, st>>>(b);
-    pp_sel_pick_batch_kernel<0><<<dim3(1, F), 1024, 0, st>>>(b);
-    pp_sel_hist_batch_kernel<1><<<dim3(hblocks, F), 256, 0, st>>>(b);
-    pp_sel_pick_batch_kernel<1><<<dim3(1, F), 1024, 0, st>>>(b);
-    pp_sel_compact_batch_kernel<<<dim3(blocks, F), 256, 0, st>>>(b);
-    pp_sel_sort_batch_kernel<<<dim3(1, F), 1024, 0, st>>>(b);
-    pp_iou_batch_kernel<<<dim3((unsigned)p.topk, F), 256, 0, st>>>(b);
-    pp_sweep_batch_kernel<<<dim3(1, F), 1024, 0, st>>>(b);
-    return hip_check(hipGetLastError(), who);
+    return postprocess_run(b, frames, ws + bl.cub, bl.cub_bytes, stream, who);
 }
 
 #ifdef QV2X_PP_FINE

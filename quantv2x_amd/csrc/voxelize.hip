@@ -2,158 +2,239 @@
 // spconv.utils.Point2VoxelCPU3d (opencood/data_utils/pre_processor/sp_voxel_preprocessor.py:54-85).  spconv is not
 // vendored by the reference, so this implements the *contract* stated in quantv2x_amd/synth.py / oracle/voxelize.py:
 //   voxels in order of first point appearance, first-come <= max_points points per voxel, <= max_voxels voxels,
-//   coords (z, y, x), zero padded -- deterministically (no atomics decide an order):
-//   1. cell id per point (float32 arithmetic identical to the numpy statement), key = cell << 20 | point index
-//   2. one device radix sort of the keys  (hipCUB; points of a cell become contiguous, in index order)
-//   3. segment heads -> rank of each point inside its cell; flag the first point of every cell
-//   4. exclusive scan of the flags in point order = voxel number in order of first appearance
-//   5. scatter points / coords / counts
+//   coords (z, y, x), zero padded -- deterministically (no atomics decide an order).
+// ONE implementation for a batch of 1..64 sweeps per call; qv2x_voxelize_f32 is the batch of one sweep (a per-sweep call is a clear, a
+// key kernel, a radix sort, two scans and two more kernels, 84 us of launches -- at 32 sweeps longer than half a model step, hence the batch):
+//   key = sweep << (cell bits + 20) | cell << 20 | index of the point inside its sweep
+//   1. cell id per point (float32 arithmetic identical to the numpy statement); keys of all sweeps into one array (sweep s at offset
+//      off[s] = points of the sweeps before it)
+//   2. ONE device radix sort (hipCUB) over the bits in use: points of a (sweep, cell) become contiguous, in index order
+//   3. segment heads (a sweep change is a key change) -> rank of each point inside its cell; flag the first point of every cell
+//   4. ONE exclusive sum of the flags over the concatenated points, in point order: a sweep's voxel numbers (order of first appearance) =
+//      the sum minus its value at the sweep's first point (the flags of the sweeps before it)
+//   5. scatter points / coords / counts into the sweep's slab of `capacity` rows
+// The number of launches does not depend on the number of sweeps; the table of sweep pointers travels as a kernel argument.
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
 
 namespace qv2x {
 
-constexpr unsigned long long INVALID_KEY = ~0ull;
+namespace {
 
-struct VoxGrid {
+constexpr unsigned long long INVALID_KEY = ~0ull;
+constexpr int MAX_SWEEPS = 64, IDX_BITS = 20;
+
+struct VoxBatch {
+    const float4* pts[MAX_SWEEPS];
+    int off[MAX_SWEEPS + 1];                                       // off[s] = points of the sweeps before s; off[n] = all points
     float lo[3], vs[3];
     int nx, ny, nz;
+    int n, sweep_shift;                                            // sweep_shift = IDX_BITS + cell bits
 };
 
-__global__ void vox_keys_kernel(const float4* __restrict__ pts, int P, VoxGrid g, unsigned long long* __restrict__ keys) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P) return;
-    const float4 p = pts[i];
-    const float fx = floorf((p.x - g.lo[0]) / g.vs[0]), fy = floorf((p.y - g.lo[1]) / g.vs[1]), fz = floorf((p.z - g.lo[2]) / g.vs[2]);
-    const bool ok = fx >= 0.f && fx < (float)g.nx && fy >= 0.f && fy < (float)g.ny && fz >= 0.f && fz < (float)g.nz;
-    const unsigned long long cell = ((unsigned long long)fz * g.ny + (unsigned long long)fy) * g.nx + (unsigned long long)fx;
-    keys[i] = ok ? ((cell << 20) | (unsigned)i) : INVALID_KEY;
+// grid (blocks of the longest sweep, sweeps)
+__global__ void vox_keys_kernel(const VoxBatch b, unsigned long long* __restrict__ keys) {
+    const int s = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int base = b.off[s];
+    if (i >= b.off[s + 1] - base) return;
+    const float4 p = b.pts[s][i];
+    const float fx = floorf((p.x - b.lo[0]) / b.vs[0]), fy = floorf((p.y - b.lo[1]) / b.vs[1]), fz = floorf((p.z - b.lo[2]) / b.vs[2]);
+    const bool ok = fx >= 0.f && fx < (float)b.nx && fy >= 0.f && fy < (float)b.ny && fz >= 0.f && fz < (float)b.nz;
+    const unsigned long long cell = ((unsigned long long)fz * b.ny + (unsigned long long)fy) * b.nx + (unsigned long long)fx;
+    // a valid key never has all sweep bits set (the field holds the VALUE n too), so the invalid ones sort behind every sweep
+    keys[base + i] = ok ? (((unsigned long long)s << b.sweep_shift) | (cell << IDX_BITS) | (unsigned)i) : INVALID_KEY;
 }
 
-// sorted position j: head[j] = j if the cell changes here else 0; first_flag[point index] = 1 for the head point of a cell
-__global__ void vox_heads_kernel(const unsigned long long* __restrict__ keys, int P, int* __restrict__ head, int* __restrict__ first_flag) {
+// sorted position j: head[j] = j if the (sweep, cell) changes here else 0; first_flag[off[sweep] + point index] = 1 for the head point
+__global__ void vox_heads_kernel(const VoxBatch b, const unsigned long long* __restrict__ keys, int P, int* __restrict__ head,
+                                  int* __restrict__ first_flag) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= P) return;
     const unsigned long long k = keys[j];
     const bool valid = k != INVALID_KEY;
-    const bool is_head = valid && (j == 0 || (keys[j - 1] >> 20) != (k >> 20));
+    const bool is_head = valid && (j == 0 || (keys[j - 1] >> IDX_BITS) != (k >> IDX_BITS));
     head[j] = is_head ? j : 0;
-    if (is_head) first_flag[(int)(k & 0xFFFFF)] = 1;
+    if (is_head) first_flag[b.off[(int)(k >> b.sweep_shift)] + (int)(k & 0xFFFFF)] = 1;
 }
 
-__global__ void vox_scatter_kernel(const float4* __restrict__ pts, const unsigned long long* __restrict__ keys,
-                                   const int* __restrict__ head, const int* __restrict__ vox_of_first, int P, VoxGrid g,
-                                   int agent, int max_points, int max_voxels, float4* __restrict__ feats,
-                                   int4* __restrict__ coords, int* __restrict__ nump, int* __restrict__ count) {
+__global__ void vox_scatter_kernel(const VoxBatch b, const unsigned long long* __restrict__ keys, const int* __restrict__ head,
+                                    const int* __restrict__ vox_of_first, int P, int first_agent, int max_points, int capacity,
+                                    float4* __restrict__ feats, int4* __restrict__ coords, int* __restrict__ nump) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= P) return;
     const unsigned long long k = keys[j];
     if (k == INVALID_KEY) return;
-    const int h = head[j];                                   // sorted position of this cell's first point (after the max-scan)
-    const int v = vox_of_first[(int)(keys[h] & 0xFFFFF)];    // voxel number = cells whose first point comes earlier
-    if (v >= max_voxels) return;
+    const int s = (int)(k >> b.sweep_shift), base = b.off[s];
+    const int h = head[j];                                         // sorted position of this cell's first point (after the max-scan)
+    // voxel number inside the sweep = its cells whose first point comes earlier
+    const int v = vox_of_first[base + (int)(keys[h] & 0xFFFFF)] - vox_of_first[base];
+    if (v >= capacity) return;
+    const size_t row = (size_t)s * capacity + v;
     const int rank = j - h, idx = (int)(k & 0xFFFFF);
-    if (rank < max_points) feats[(size_t)v * max_points + rank] = pts[idx];
-    const bool last = (j + 1 == P) || (keys[j + 1] == INVALID_KEY) || ((keys[j + 1] >> 20) != (k >> 20));
+    if (rank < max_points) feats[row * max_points + rank] = b.pts[s][idx];
+    const bool last = (j + 1 == P) || (keys[j + 1] == INVALID_KEY) || ((keys[j + 1] >> IDX_BITS) != (k >> IDX_BITS));
     if (last) {
-        const unsigned long long cell = k >> 20;
-        const int cx = (int)(cell % g.nx), cy = (int)((cell / g.nx) % g.ny), cz = (int)(cell / ((unsigned long long)g.nx * g.ny));
-        coords[v] = make_int4(agent, cz, cy, cx);
-        nump[v] = rank + 1 < max_points ? rank + 1 : max_points;
-        atomicMax(count, v + 1);                              // number of voxels = highest voxel number + 1 (order independent)
+        const unsigned long long cell = (k >> IDX_BITS) & ((1ull << (b.sweep_shift - IDX_BITS)) - 1ull);
+        const int cx = (int)(cell % b.nx), cy = (int)((cell / b.nx) % b.ny), cz = (int)(cell / ((unsigned long long)b.nx * b.ny));
+        coords[row] = make_int4(first_agent + s, cz, cy, cx);
+        nump[row] = rank + 1 < max_points ? rank + 1 : max_points;
     }
 }
 
 // Clears done by a kernel, not by hipMemsetAsync / hipMemcpyAsync nodes: inside a captured hipGraph a memset node did not stay ordered
 // before the kernel that follows it on later replays (found on the SECOND encoder, csrc/sparse_conv.hip) -- and the whole pre-step is
-// meant to be captured with the model behind it.  Rows past the voxel count are left in a defined state: coords (-1, -1, -1, -1)
-// -- the agent index the PFN kernel drops -- zero points, zero features: a caller may hand ALL max_voxels rows to the model and never
+// meant to be captured with the model behind it.  Rows past a sweep's voxel count are left in a defined state: coords (-1, -1, -1, -1)
+// -- the agent index the PFN kernel drops -- zero points, zero features: a caller may hand ALL `capacity` rows to the model and never
 // read the count back.
 __global__ void vox_clear_kernel(int4* __restrict__ flags4, long long nflags4, int4* __restrict__ feats4, long long nfeats4,
-                                 int4* __restrict__ coords, int* __restrict__ nump, int max_voxels, int* __restrict__ count) {
+                                  int4* __restrict__ coords, int* __restrict__ nump, long long rows) {
     const long long stride = (long long)gridDim.x * blockDim.x;
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) *count = 0;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     for (long long k = i; k < nflags4; k += stride) flags4[k] = make_int4(0, 0, 0, 0);
     for (long long k = i; k < nfeats4; k += stride) feats4[k] = make_int4(0, 0, 0, 0);
-    for (long long k = i; k < max_voxels; k += stride) { coords[k] = make_int4(-1, -1, -1, -1); nump[k] = 0; }
+    for (long long k = i; k < rows; k += stride) { coords[k] = make_int4(-1, -1, -1, -1); nump[k] = 0; }
 }
 
-__global__ void vox_count_kernel(const int* __restrict__ count, int max_voxels, int* __restrict__ out) { *out = *count < max_voxels ? *count : max_voxels; }
+// voxels of a sweep = the first-point flags of its points = the exclusive sum at the next sweep's first point minus its own (the last
+// sweep with points: the sum's total), capped.  No atomic: a per-sweep atomicMax from the scatter kernel -- fine for ONE sweep, where the
+// compiler folds a wave's same-address atomics into one -- has a DIVERGENT address in a batch and serialised on one cache line: 7.3 ms of
+// an 8.3 ms call at 32 sweeps.
+__global__ void vox_count_kernel(const VoxBatch b, const int* __restrict__ vox_of_first, const int* __restrict__ first_flag, int P,
+                                  int capacity, int* __restrict__ out) {
+    const int s = threadIdx.x;
+    if (s >= b.n) return;
+    const int lo = b.off[s], hi = b.off[s + 1];
+    int c = 0;
+    if (hi > lo) c = (hi < P ? vox_of_first[hi] : vox_of_first[P - 1] + first_flag[P - 1]) - vox_of_first[lo];
+    out[s] = c < capacity ? c : capacity;
+}
 
-struct VoxWorkspace {
-    unsigned long long *keys_in, *keys_out;
-    int *head, *first_flag, *vox_of_first, *count;
-    void* cub;
-    size_t cub_bytes;
-};
+size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t cub_bytes_for(int P) {
+size_t cub_bytes_for(int P, int end_bit) {
     size_t a = 0, b = 0, c = 0;
-    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, a, (unsigned long long*)nullptr, (unsigned long long*)nullptr, P, 0, 64);
+    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, a, (unsigned long long*)nullptr, (unsigned long long*)nullptr, P, 0, end_bit);
     (void)hipcub::DeviceScan::InclusiveScan(nullptr, b, (int*)nullptr, (int*)nullptr, hipcub::Max(), P);
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, c, (int*)nullptr, (int*)nullptr, P);
     return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
+int bit_width(unsigned long long v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
+
+// all points of the batch, or -1
+long long total_points(int n_sweeps, const int32_t* n_points, const char* who) {
+    if (n_sweeps < 1 || n_sweeps > MAX_SWEEPS) { fail(QV2X_EINVAL, "%s: 1..%d sweeps", who, MAX_SWEEPS); return -1; }
+    if (!n_points) { fail(QV2X_EINVAL, "%s: null pointer", who); return -1; }
+    long long P = 0;
+    for (int s = 0; s < n_sweeps; ++s) {
+        if (n_points[s] < 0 || n_points[s] >= (1 << IDX_BITS)) { fail(QV2X_EINVAL, "%s: sweep %d: 0 <= n_points < 2^20", who, s); return -1; }
+        P += n_points[s];
+    }
+    return P;
+}
+
+// workspace for P points in all
+int64_t workspace_for(long long P) {
+    if (P == 0) return 256;                                        // (nothing is kept there: a caller may allocate what it is told)
+    return (int64_t)(2 * align_up((size_t)P * 8) + 3 * align_up((size_t)P * 4) + align_up(cub_bytes_for((int)P, 64)));
+}
+
+// both entries: the checks of a batch, then the launch sequence
+int voxelize_run(const char* who, const float* const* points, const int32_t* n_points, int n_sweeps, const float* lidar_range,
+                 const float* voxel_size, int first_agent, int max_points, int capacity, void* workspace, int64_t workspace_bytes,
+                 float* voxel_features, int32_t* voxel_coords, int32_t* voxel_num_points, int32_t* voxel_counts, void* stream) {
+    const long long Pll = total_points(n_sweeps, n_points, who);
+    if (Pll < 0) return QV2X_EINVAL;
+    if (!points || !lidar_range || !voxel_size || !workspace || !voxel_features || !voxel_coords || !voxel_num_points || !voxel_counts)
+        return fail(QV2X_EINVAL, "%s: null pointer", who);
+    if (max_points <= 0 || capacity <= 0) return fail(QV2X_EINVAL, "%s: max_points > 0, capacity > 0", who);
+    if ((long long)n_sweeps * capacity >= (1ll << 31)) return fail(QV2X_EINVAL, "%s: n_sweeps * capacity must stay below 2^31", who);
+    if (workspace_bytes < workspace_for(Pll)) return fail(QV2X_EINVAL, "%s: workspace too small", who);
+    if ((uintptr_t)voxel_features & 15 || (uintptr_t)voxel_coords & 15 || (uintptr_t)workspace & 15) return fail(QV2X_EALIGN, "%s: 16-byte alignment", who);
+    VoxBatch b{};
+    for (int d = 0; d < 3; ++d) { b.lo[d] = lidar_range[d]; b.vs[d] = voxel_size[d]; }
+    b.nx = (int)lrintf((lidar_range[3] - lidar_range[0]) / voxel_size[0]);
+    b.ny = (int)lrintf((lidar_range[4] - lidar_range[1]) / voxel_size[1]);
+    b.nz = (int)lrintf((lidar_range[5] - lidar_range[2]) / voxel_size[2]);
+    if (b.nx <= 0 || b.ny <= 0 || b.nz <= 0 || (long long)b.nx * b.ny * b.nz >= (1ll << 43)) return fail(QV2X_EINVAL, "%s: bad grid", who);
+    const int cell_bits = bit_width((unsigned long long)b.nx * b.ny * b.nz - 1ull) > 0 ? bit_width((unsigned long long)b.nx * b.ny * b.nz - 1ull) : 1;
+    const int sweep_bits = bit_width((unsigned long long)n_sweeps);             // holds the value n_sweeps itself: no valid key is all ones
+    if (sweep_bits + cell_bits + IDX_BITS > 64) return fail(QV2X_EINVAL, "%s: %d sweep bits + %d cell bits + 20 index bits exceed the 64-bit key", who, sweep_bits, cell_bits);
+    b.n = n_sweeps; b.sweep_shift = IDX_BITS + cell_bits;
+    int longest = 0;
+    for (int s = 0; s < n_sweeps; ++s) {
+        if (n_points[s] > 0 && (!points[s] || ((uintptr_t)points[s] & 15))) return fail(points[s] ? QV2X_EALIGN : QV2X_EINVAL, "%s: sweep %d: null or unaligned points", who, s);
+        b.pts[s] = (const float4*)points[s];
+        b.off[s + 1] = b.off[s] + n_points[s];
+        if (n_points[s] > longest) longest = n_points[s];
+    }
+    const int P = (int)Pll;
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)workspace;
+    unsigned long long *keys_in = nullptr, *keys_out = nullptr;
+    int *head = nullptr, *first_flag = nullptr, *vox_of_first = nullptr;
+    if (P > 0) {
+        keys_in = (unsigned long long*)w; w += align_up((size_t)P * 8);
+        keys_out = (unsigned long long*)w; w += align_up((size_t)P * 8);
+        head = (int*)w; w += align_up((size_t)P * 4);
+        first_flag = (int*)w; w += align_up((size_t)P * 4);
+        vox_of_first = (int*)w; w += align_up((size_t)P * 4);
+    }
+    void* cub = w;
+    const size_t cub_bytes = (size_t)workspace_bytes - (size_t)(w - (char*)workspace);
+    const long long rows = (long long)n_sweeps * capacity;
+    vox_clear_kernel<<<2048, 256, 0, st>>>((int4*)first_flag, P > 0 ? (long long)(align_up((size_t)P * 4) / 16) : 0, (int4*)voxel_features,
+                                            rows * max_points, (int4*)voxel_coords, voxel_num_points, rows);
+    if (P > 0) {
+        const int end_bit = b.sweep_shift + sweep_bits;
+        if (cub_bytes_for(P, end_bit) > cub_bytes) return fail(QV2X_EINVAL, "%s: workspace too small for the sort", who);
+        const int B = 256, G = (P + B - 1) / B;
+        int rc;
+        vox_keys_kernel<<<dim3((unsigned)((longest + B - 1) / B), (unsigned)n_sweeps), B, 0, st>>>(b, keys_in);
+        size_t tb = cub_bytes;
+        if ((rc = hip_check(hipcub::DeviceRadixSort::SortKeys(cub, tb, keys_in, keys_out, P, 0, end_bit, st), "voxelize batch sort"))) return rc;
+        vox_heads_kernel<<<G, B, 0, st>>>(b, keys_out, P, head, first_flag);
+        tb = cub_bytes;
+        if ((rc = hip_check(hipcub::DeviceScan::InclusiveScan(cub, tb, head, head, hipcub::Max(), P, st), "voxelize batch scan"))) return rc;
+        tb = cub_bytes;
+        if ((rc = hip_check(hipcub::DeviceScan::ExclusiveSum(cub, tb, first_flag, vox_of_first, P, st), "voxelize batch scan"))) return rc;
+        vox_scatter_kernel<<<G, B, 0, st>>>(b, keys_out, head, vox_of_first, P, first_agent, max_points, capacity, (float4*)voxel_features,
+                                             (int4*)voxel_coords, voxel_num_points);
+    }
+    vox_count_kernel<<<1, MAX_SWEEPS, 0, st>>>(b, vox_of_first, first_flag, P, capacity, voxel_counts);
+    return hip_check(hipGetLastError(), who);
+}
+
+}  // namespace
+
 }  // namespace qv2x
 
-extern "C" int64_t qv2x_voxelize_workspace_bytes(int n_points) {
-    using namespace qv2x;
-    if (n_points <= 0) return 0;
-    const size_t P = (size_t)n_points;
-    return (int64_t)(2 * align_up(P * 8) + 3 * align_up(P * 4) + 256 + align_up(cub_bytes_for(n_points)));
+extern "C" int64_t qv2x_voxelize_batch_workspace_bytes(int n_sweeps, const int32_t* n_points) {
+    const long long P = qv2x::total_points(n_sweeps, n_points, "qv2x_voxelize_batch_workspace_bytes");
+    return P < 0 ? -1 : qv2x::workspace_for(P);
 }
+
+extern "C" int qv2x_voxelize_batch_f32(const float* const* points, const int32_t* n_points, int n_sweeps, const float* lidar_range,
+                                       const float* voxel_size, int first_agent, int max_points, int capacity, void* workspace,
+                                       int64_t workspace_bytes, float* voxel_features, int32_t* voxel_coords, int32_t* voxel_num_points,
+                                       int32_t* voxel_counts, void* stream) {
+    return qv2x::voxelize_run("qv2x_voxelize_batch_f32", points, n_points, n_sweeps, lidar_range, voxel_size, first_agent, max_points, capacity,
+                              workspace, workspace_bytes, voxel_features, voxel_coords, voxel_num_points, voxel_counts, stream);
+}
+
+// one sweep: the batch of one, behind this entry's own (narrower) argument contract -- an empty sweep is refused here
+extern "C" int64_t qv2x_voxelize_workspace_bytes(int n_points) { return n_points <= 0 ? 0 : qv2x::workspace_for(n_points); }
 
 extern "C" int qv2x_voxelize_f32(const float* points, int n_points, const float* lidar_range, const float* voxel_size, int agent,
                                  int max_points, int max_voxels, void* workspace, int64_t workspace_bytes,
                                  float* voxel_features, int32_t* voxel_coords, int32_t* voxel_num_points, int32_t* n_voxels,
                                  void* stream) {
     using namespace qv2x;
-    if (!points || !lidar_range || !voxel_size || !workspace || !voxel_features || !voxel_coords || !voxel_num_points || !n_voxels)
-        return fail(QV2X_EINVAL, "qv2x_voxelize_f32: null pointer");
-    if (n_points <= 0 || n_points >= (1 << 20) || max_points <= 0 || max_voxels <= 0)
-        return fail(QV2X_EINVAL, "qv2x_voxelize_f32: 0 < n_points < 2^20, max_points > 0, max_voxels > 0");
-    if (workspace_bytes < qv2x_voxelize_workspace_bytes(n_points)) return fail(QV2X_EINVAL, "qv2x_voxelize_f32: workspace too small");
-    if ((uintptr_t)points & 15 || (uintptr_t)voxel_features & 15 || (uintptr_t)voxel_coords & 15) return fail(QV2X_EALIGN, "qv2x_voxelize_f32: 16-byte alignment");
-    VoxGrid g;
-    for (int d = 0; d < 3; ++d) { g.lo[d] = lidar_range[d]; g.vs[d] = voxel_size[d]; }
-    g.nx = (int)lrintf((lidar_range[3] - lidar_range[0]) / voxel_size[0]);
-    g.ny = (int)lrintf((lidar_range[4] - lidar_range[1]) / voxel_size[1]);
-    g.nz = (int)lrintf((lidar_range[5] - lidar_range[2]) / voxel_size[2]);
-    if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0 || (long long)g.nx * g.ny * g.nz >= (1ll << 43)) return fail(QV2X_EINVAL, "qv2x_voxelize_f32: bad grid");
-    const int P = n_points;
-    hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    VoxWorkspace ws;
-    ws.keys_in = (unsigned long long*)w; w += align_up((size_t)P * 8);
-    ws.keys_out = (unsigned long long*)w; w += align_up((size_t)P * 8);
-    ws.head = (int*)w; w += align_up((size_t)P * 4);
-    ws.first_flag = (int*)w; w += align_up((size_t)P * 4);
-    ws.vox_of_first = (int*)w; w += align_up((size_t)P * 4);
-    ws.count = (int*)w; w += 256;
-    ws.cub = w; ws.cub_bytes = (size_t)workspace_bytes - (size_t)(w - (char*)workspace);
-
-    int rc;
-    {
-        const long long nflags4 = (long long)(align_up((size_t)P * 4) / 16), nfeats4 = (long long)max_voxels * max_points;
-        vox_clear_kernel<<<2048, 256, 0, st>>>((int4*)ws.first_flag, nflags4, (int4*)voxel_features, nfeats4, (int4*)voxel_coords,
-                                                voxel_num_points, max_voxels, ws.count);
-    }
-    const int B = 256, G = (P + B - 1) / B;
-    vox_keys_kernel<<<G, B, 0, st>>>((const float4*)points, P, g, ws.keys_in);
-    size_t tb = ws.cub_bytes;
-    if ((rc = hip_check(hipcub::DeviceRadixSort::SortKeys(ws.cub, tb, ws.keys_in, ws.keys_out, P, 0, 64, st), "voxelize sort"))) return rc;
-    vox_heads_kernel<<<G, B, 0, st>>>(ws.keys_out, P, ws.head, ws.first_flag);
-    tb = ws.cub_bytes;
-    if ((rc = hip_check(hipcub::DeviceScan::InclusiveScan(ws.cub, tb, ws.head, ws.head, hipcub::Max(), P, st), "voxelize scan"))) return rc;
-    tb = ws.cub_bytes;
-    if ((rc = hip_check(hipcub::DeviceScan::ExclusiveSum(ws.cub, tb, ws.first_flag, ws.vox_of_first, P, st), "voxelize scan"))) return rc;
-    vox_scatter_kernel<<<G, B, 0, st>>>((const float4*)points, ws.keys_out, ws.head, ws.vox_of_first, P, g, agent, max_points, max_voxels,
-                                        (float4*)voxel_features, (int4*)voxel_coords, voxel_num_points, ws.count);
-    vox_count_kernel<<<1, 1, 0, st>>>(ws.count, max_voxels, n_voxels);
-    return hip_check(hipGetLastError(), "qv2x_voxelize_f32 launch");
+    const char* who = "qv2x_voxelize_f32";
+    // what the batch does not refuse; everything else (ranges, null pointers, workspace size, 16-byte alignment) is its own check
+    if (!points || n_points <= 0) return fail(QV2X_EINVAL, "%s: points must not be null, 0 < n_points < 2^20", who);
+    const int32_t n = n_points;
+    return voxelize_run(who, &points, &n, 1, lidar_range, voxel_size, agent, max_points, max_voxels, workspace, workspace_bytes,
+                        voxel_features, voxel_coords, voxel_num_points, n_voxels, stream);
 }

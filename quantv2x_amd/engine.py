@@ -289,28 +289,34 @@ def split_heads(preds: torch.Tensor, splits, suffix: str = "") -> dict:
     return out
 
 
-def capture_forward(module: nn.Module, data_dict: dict):
-    """Capture one ``module.forward(data_dict)`` into a HIP graph (torch.cuda.CUDAGraph on ROCm) after two warm-up forwards on a side stream.
-    The returned callable replays it on the same input tensors (refresh their contents in place between replays) and returns the same
-    output dict; ``replay.graph`` is the graph.  A device ``record_len`` is replaced by a CPU copy: its values shape the launch list."""
-    rl = data_dict.get("record_len")
-    if data_dict["pairwise_t_matrix"].shape[0] > 1 and isinstance(rl, torch.Tensor) and rl.is_cuda:
-        data_dict = dict(data_dict, record_len=rl.cpu())
+def capture_call(call):
+    """Capture one ``call()`` (no arguments) into a HIP graph (torch.cuda.CUDAGraph on ROCm) after two warm-up calls on a side stream.
+    The returned callable replays it and returns what ``call`` returned; ``replay.graph`` is the graph."""
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         for _ in range(2):
-            module.forward(data_dict)
+            call()
     torch.cuda.current_stream().wait_stream(side)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        out = module.forward(data_dict)
+        out = call()
 
     def replay():
         graph.replay()
         return out
     replay.graph = graph
     return replay
+
+
+def capture_forward(module: nn.Module, data_dict: dict):
+    """Capture one ``module.forward(data_dict)`` into a HIP graph (``capture_call``).  The returned callable replays it on the same input
+    tensors (refresh their contents in place between replays) and returns the same output dict; ``replay.graph`` is the graph.  A device
+    ``record_len`` is replaced by a CPU copy: its values shape the launch list."""
+    rl = data_dict.get("record_len")
+    if data_dict["pairwise_t_matrix"].shape[0] > 1 and isinstance(rl, torch.Tensor) and rl.is_cuda:
+        data_dict = dict(data_dict, record_len=rl.cpu())
+    return capture_call(lambda: module.forward(data_dict))
 
 
 def assemble_heter_codes(owner: str, engines: dict, slot_cache: dict, agents: list, data_dict: dict, encode, taps: Optional[dict]) -> torch.Tensor:

@@ -9,6 +9,7 @@ from typing import Sequence
 import numpy as np
 import torch
 
+from .engine import capture_call
 from .plugin.data_utils.post_processor.voxel_postprocessor import gpu_post_process_batch
 from .voxelizer import GpuVoxelizer
 
@@ -53,21 +54,7 @@ class PointsToBoxes:
         return {"corners": corners, "scores": scores, "labels": labels, "counts": counts, "voxel_counts": inp["voxel_counts"]}
 
     def capture(self, sweeps: Sequence[torch.Tensor], transforms: torch.Tensor = None):
-        """Capture one call into a HIP graph after two warm-up calls on a side stream (the pattern of ``engine.capture_forward``).  The
-        returned callable replays it on the same sweep tensors -- refresh their contents in place between replays, the point counts stay
-        -- and returns the same output dict; ``replay.graph`` is the graph."""
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self(sweeps, transforms)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self(sweeps, transforms)
-
-        def replay():
-            graph.replay()
-            return out
-        replay.graph = graph
-        return replay
+        """Capture one call into a HIP graph (``engine.capture_call``: two warm-up calls on a side stream first).  The returned callable
+        replays it on the same sweep tensors -- refresh their contents in place between replays, the point counts stay -- and returns the
+        same output dict; ``replay.graph`` is the graph."""
+        return capture_call(lambda: self(sweeps, transforms))

@@ -26,6 +26,29 @@ def load_point_pillar_anchor_args(hypes: dict) -> dict:
     return hypes
 
 
+def _desc(owner, maps, *, anchors_per_cell, num_classes, num_bins, dir_offset, rng, range_xy_only, max_extent, z_lim, max_boxes) -> PostprocessDesc:
+    """the descriptor of a call on head maps ``[N, C, H, W]`` (``transform`` left to the caller: only the single-CAV C entry reads it)"""
+    d = PostprocessDesc()
+    d.h, d.w, d.anchors_per_cell, d.num_bins = int(maps.shape[2]), int(maps.shape[3]), anchors_per_cell, num_bins
+    d.score_threshold = float(owner.params["target_args"]["score_threshold"])
+    d.nms_threshold = float(owner.params["nms_thresh"])
+    d.dir_offset = dir_offset
+    for i, v in enumerate(rng):
+        d.range[i] = float(v)
+    d.max_boxes, d.num_classes, d.range_xy_only = max_boxes, num_classes, int(range_xy_only)
+    d.max_extent, d.z_min, d.z_max = max_extent, z_lim[0], z_lim[1]
+    return d
+
+
+def _workspace(owner, need: int, dev, query: str):
+    """``owner``'s workspace, kept between frames and grown to ``need`` bytes on ``dev`` (a negative ``need`` is ``query``'s refusal)"""
+    if need < 0:
+        check(-1, query)
+    if owner._ws is None or owner._ws.numel() < need or owner._ws.device != dev:
+        owner._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ptr(owner._ws)
+
+
 def gpu_post_process(owner, cls, reg, dirp, anchors_dev, transformation_matrix, *, anchors_per_cell, num_classes, num_bins, dir_offset,
                      rng, range_xy_only, max_extent, z_lim, max_boxes, sync=True):
     """One ``qv2x_postprocess_f32`` call (or, when ``cls`` / ``reg`` / ``dirp`` / ``anchors_dev`` / ``transformation_matrix`` are lists with
@@ -39,13 +62,8 @@ def gpu_post_process(owner, cls, reg, dirp, anchors_dev, transformation_matrix, 
     t_l = list(transformation_matrix) if many else [transformation_matrix]
     ncav = len(cls_l)
     dev = cls_l[0].device
-    d = PostprocessDesc()
-    d.h, d.w, d.anchors_per_cell, d.num_bins = int(cls_l[0].shape[2]), int(cls_l[0].shape[3]), anchors_per_cell, num_bins
-    d.score_threshold = float(owner.params["target_args"]["score_threshold"])
-    d.nms_threshold = float(owner.params["nms_thresh"])
-    d.dir_offset = dir_offset
-    for i, v in enumerate(rng):
-        d.range[i] = float(v)
+    d = _desc(owner, cls_l[0], anchors_per_cell=anchors_per_cell, num_classes=num_classes, num_bins=num_bins, dir_offset=dir_offset,
+              rng=rng, range_xy_only=range_xy_only, max_extent=max_extent, z_lim=z_lim, max_boxes=max_boxes)
     tf = (C.c_float * (16 * ncav))()
     for c, t in enumerate(t_l):
         t = np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.float32).reshape(16)
@@ -53,13 +71,8 @@ def gpu_post_process(owner, cls, reg, dirp, anchors_dev, transformation_matrix, 
             tf[c * 16 + i] = float(t[i])
             if c == 0:
                 d.transform[i] = float(t[i])
-    d.max_boxes, d.num_classes, d.range_xy_only = max_boxes, num_classes, int(range_xy_only)
-    d.max_extent, d.z_min, d.z_max = max_extent, z_lim[0], z_lim[1]
     need = lib.qv2x_postprocess_late_workspace_bytes(C.byref(d), ncav)
-    if need < 0:
-        check(-1, "qv2x_postprocess_late_workspace_bytes")
-    if owner._ws is None or owner._ws.numel() < need or owner._ws.device != dev:
-        owner._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace(owner, need, dev, "qv2x_postprocess_late_workspace_bytes")
     corners = torch.empty((max_boxes, 8, 3), dtype=torch.float32, device=dev)
     scores = torch.empty((max_boxes,), dtype=torch.float32, device=dev)
     labels = torch.empty((max_boxes,), dtype=torch.int32, device=dev)
@@ -68,7 +81,7 @@ def gpu_post_process(owner, cls, reg, dirp, anchors_dev, transformation_matrix, 
     cls_l, reg_l = [f32(x) for x in cls_l], [f32(x) for x in reg_l]
     dir_l = [f32(x) if (x is not None and num_bins > 0) else None for x in dir_l]
     arr = lambda ts: (C.c_void_p * ncav)(*[(t.data_ptr() if t is not None else None) for t in ts])
-    check(lib.qv2x_postprocess_late_f32(C.byref(d), ncav, arr(cls_l), arr(reg_l), arr(dir_l), arr(anc_l), tf, ptr(owner._ws), need,
+    check(lib.qv2x_postprocess_late_f32(C.byref(d), ncav, arr(cls_l), arr(reg_l), arr(dir_l), arr(anc_l), tf, ws, need,
                                         ptr(corners), ptr(scores), ptr(labels), ptr(count), current_stream()), "qv2x_postprocess_late_f32")
     if not sync:                                     # HIP-graph capture: fixed-size outputs + the box count left on the device
         return corners, scores, labels, count
@@ -101,25 +114,15 @@ def gpu_post_process_batch(owner, cls, reg, dirp, anchors_dev, transformation_ma
     what ``gpu_post_process`` returns for that frame."""
     lib = load()
     frames, dev = int(cls.shape[0]), cls.device
-    d = PostprocessDesc()
-    d.h, d.w, d.anchors_per_cell, d.num_bins = int(cls.shape[2]), int(cls.shape[3]), anchors_per_cell, num_bins
-    d.score_threshold = float(owner.params["target_args"]["score_threshold"])
-    d.nms_threshold = float(owner.params["nms_thresh"])
-    d.dir_offset = dir_offset
-    for i, v in enumerate(rng):
-        d.range[i] = float(v)
-    d.max_boxes, d.num_classes, d.range_xy_only = max_boxes, num_classes, int(range_xy_only)
-    d.max_extent, d.z_min, d.z_max = max_extent, z_lim[0], z_lim[1]
+    d = _desc(owner, cls, anchors_per_cell=anchors_per_cell, num_classes=num_classes, num_bins=num_bins, dir_offset=dir_offset,
+              rng=rng, range_xy_only=range_xy_only, max_extent=max_extent, z_lim=z_lim, max_boxes=max_boxes)
     t = torch.as_tensor(transformation_matrix)
     if tuple(t.shape) != (frames, 4, 4):
         raise ValueError(f"transformation_matrix {tuple(t.shape)}: ({frames}, 4, 4) expected")
     if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
         t = t.to(device=dev, dtype=torch.float32).contiguous()
     need = lib.qv2x_postprocess_batch_workspace_bytes(C.byref(d), frames)
-    if need < 0:
-        check(-1, "qv2x_postprocess_batch_workspace_bytes")
-    if owner._ws is None or owner._ws.numel() < need or owner._ws.device != dev:
-        owner._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace(owner, need, dev, "qv2x_postprocess_batch_workspace_bytes")
     corners = torch.empty((frames, max_boxes, 8, 3), dtype=torch.float32, device=dev)
     scores = torch.empty((frames, max_boxes), dtype=torch.float32, device=dev)
     labels = torch.empty((frames, max_boxes), dtype=torch.int32, device=dev)
@@ -128,7 +131,7 @@ def gpu_post_process_batch(owner, cls, reg, dirp, anchors_dev, transformation_ma
     reg, rs = _frame_maps(reg, frames)
     dirp, ds = _frame_maps(dirp, frames) if (dirp is not None and num_bins > 0) else (None, 0)
     check(lib.qv2x_postprocess_batch_f32(C.byref(d), frames, ptr(cls), cs, ptr(reg), rs, ptr(dirp), ds, ptr(anchors_dev), ptr(t),
-                                         ptr(owner._ws), need, ptr(corners), ptr(scores), ptr(labels), ptr(counts), current_stream()),
+                                         ws, need, ptr(corners), ptr(scores), ptr(labels), ptr(counts), current_stream()),
           "qv2x_postprocess_batch_f32")
     return corners, scores, labels, counts
 

@@ -158,6 +158,30 @@ def test_one_frame_equals_the_single_entry(anchors):
         assert _assert_frames_equal("one_class", got, dcls, dreg, None, danc, t)[0] > 0
 
 
+@pytest.mark.parametrize("f", [2, 3])
+@pytest.mark.parametrize("cfg", list(CONFIGS))
+def test_single_entry_equals_the_oracle_on_the_crowded_frames(cfg, f, anchors):
+    """qv2x_postprocess_f32 pinned to the CPU oracle directly (the batch-vs-single comparisons above run both sides through the same
+    kernels): frame 2 -- far more candidates than max_boxes, the top-k selection cuts -- and frame 3 -- 3 000 tied top scores, the
+    selection's tie-breaking by slot -- against oracle.postprocess.post_process with the NMS looking at the MAX_BOXES best scores: same
+    boxes in the same order, labels equal, scores and corners to 1e-5 (the tolerance of tests/test_hip_postprocess.py)."""
+    ncls, nbins, xy, ext, zl = CONFIGS[cfg]
+    cls, reg, dirp = _frames(ncls, nbins)
+    fdir = None if dirp is None else dirp[f:f + 1]
+    want = P.post_process(cls[f:f + 1], reg[f:f + 1], fdir, anchors, TRANSFORMS[f], LIDAR, THR, NMS, DIR_OFFSET, nbins, True, ncls, ext, zl, xy,
+                          True, top=MAX_BOXES)
+    assert 1 <= len(want[1]) <= MAX_BOXES                                # on the CPU: the oracle keeps something
+    dev = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    corners, scores, labels, count = _single(cfg, dev(cls[f]), dev(reg[f]), None if dirp is None else dev(dirp[f]), dev(anchors.reshape(-1, 7)),
+                                             TRANSFORMS[f])
+    k = int(count)
+    print(f"{cfg} frame {f}: oracle keeps {len(want[1])}, the entry {k}")
+    assert k == len(want[1])
+    np.testing.assert_array_equal(labels[:k].cpu().numpy(), want[2])
+    np.testing.assert_allclose(scores[:k].cpu().numpy(), want[1], rtol=0, atol=1e-5)
+    np.testing.assert_allclose(corners[:k].cpu().numpy(), want[0], rtol=0, atol=1e-5)
+
+
 def test_frames_at_a_stride(anchors):
     """head maps that are a slice of a larger tensor (the model's stacked cls | reg | dir predictions): taken where they are"""
     from quantv2x_amd.plugin.data_utils.post_processor import voxel_postprocessor as V

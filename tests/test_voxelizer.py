@@ -36,6 +36,54 @@ def test_gpu_voxelizer_small(n, max_points, max_voxels):
     np.testing.assert_array_equal(f.cpu().numpy(), rf)
 
 
+def _edge_sweep(case):
+    """the smallest sweeps of the one-sweep key layout -> (points, max_points, max_voxels)"""
+    g = np.random.default_rng(7)
+    lo, hi, vs = np.asarray(RANGE[:3]), np.asarray(RANGE[3:]), np.asarray(VS)
+    if case == "one_point":
+        return np.array([[lo[0] + 2.5 * vs[0], hi[1] - 0.5 * vs[1], -1.0, 0.5]], np.float32), 32, 64
+    if case == "all_outside":
+        pts = _cloud(300, 3)
+        pts[:150, 0] = hi[0] + g.uniform(0.01, 5.0, 150)                 # beyond +x
+        pts[150:, 1] = lo[1] - g.uniform(0.01, 5.0, 150)                 # beyond -y
+        return pts, 32, 64
+    cells = g.choice(int((hi[0] - lo[0]) / vs[0]) * int((hi[1] - lo[1]) / vs[1]), size=40, replace=False)       # "both_caps"
+    nx = int((hi[0] - lo[0]) / vs[0])
+    centre = np.stack([lo[0] + (cells % nx + 0.5) * vs[0], lo[1] + (cells // nx + 0.5) * vs[1]], 1)
+    of = g.integers(0, 40, 2000)
+    xy = centre[of] + g.uniform(-0.3, 0.3, (2000, 2)) * vs[:2]
+    return np.concatenate([xy, g.uniform(-2.5, 0.5, (2000, 1)), g.uniform(0, 1, (2000, 1))], 1).astype(np.float32), 4, 16
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["one_point", "all_outside", "both_caps"])
+def test_gpu_voxelizer_one_sweep_edge_shapes(case):
+    """``one`` and ``fixed([pts], cap)`` -- a batch of ONE sweep underneath -- against the plain-Python contract, exactly: a single valid
+    point; no valid point at all (count 0, every row in the defined tail state); ~40 cells of 50 points with 16 voxels of 4 points allowed
+    (the voxel cap and the per-voxel cap both bite)."""
+    import torch
+    from quantv2x_amd.voxelizer import GpuVoxelizer
+    pts, max_points, max_voxels = _edge_sweep(case)
+    rf, rc, rm = ref_voxelize(pts, RANGE, VS, max_points, max_voxels)
+    full = ref_voxelize(pts, RANGE, VS, 10 ** 6, 10 ** 6)[2]            # on the CPU: the sweep is the case it is meant to be
+    assert {"one_point": len(pts) == 1 and len(rm) == 1, "all_outside": len(pts) == 300 and len(rm) == 0,
+            "both_caps": len(pts) == 2000 and 35 <= len(full) <= 40 and len(rm) == 16 and full[:16].min() > 4}[case]
+    vz = GpuVoxelizer(RANGE, VS, max_points, max_voxels)
+    dev = torch.from_numpy(pts).cuda()
+    f, c, m = vz.one(dev, agent=2)
+    assert torch.equal(f.cpu(), torch.from_numpy(rf)) and torch.equal(m.cpu(), torch.from_numpy(rm))
+    assert torch.equal(c.cpu()[:, 1:], torch.from_numpy(rc)) and (c[:, 0] == 2).all()
+    for cap in (max_voxels, 64):
+        wf, wc, wm = ref_voxelize(pts, RANGE, VS, max_points, cap)
+        k = len(wm)
+        o = vz.fixed([dev], cap)
+        assert o["voxel_features"].shape == (cap, max_points, 4) and int(o["voxel_counts"][0]) == k
+        assert torch.equal(o["voxel_features"][:k].cpu(), torch.from_numpy(wf)) and torch.equal(o["voxel_num_points"][:k].cpu(), torch.from_numpy(wm))
+        assert torch.equal(o["voxel_coords"][:k, 1:].cpu(), torch.from_numpy(wc)) and (o["voxel_coords"][:k, 0] == 0).all()
+        # the rows past the count: coords -1, zero points, zero features
+        assert (o["voxel_coords"][k:] == -1).all() and (o["voxel_num_points"][k:] == 0).all() and (o["voxel_features"][k:] == 0).all()
+
+
 @pytest.mark.gpu
 def test_gpu_voxelizer_empty_sweep():
     """a sweep with no point gives no pillar (and an agent without pillars is a valid model input)"""
