@@ -325,7 +325,11 @@ int qv2x_dequant_i8_f32(const int8_t* in, int n, int h, int w, int c, int zp, fl
 /* a11.  1x1 QuantModule heads (heter_model_baseline.py:128-133,242-260) on fp32 rows:
  *     y = fma chain over ci (acc0 = bias[co]);  out = (clamp(rint(y / da[co]) + za[co], 0, 255) - za[co]) * da[co]
  *   x f32 [R][256]; w f32 [64][cout_pad][4] (k0, k2, k1, k3 order; cout_pad = cout rounded up to 32, zero filled); bias/da/za f32 [cout_pad]
- *   (da[co] <= 0 disables the output quantizer for that channel); out f32 NCHW [B][cout][hw] with R = B * hw. */
+ *   (da[co] <= 0 disables the output quantizer for that channel); out f32 NCHW [B][cout][hw] with R = B * hw.
+ *   cout_pad is 32, 64 or 96 and may exceed cout rounded up to 32; w, bias, da and za hold cout_pad channels, and the padding channels
+ *   [cout, cout_pad) must carry da <= 0 (their sums are computed and dropped: only channels below cout are stored).  hw need not divide
+ *   a 32-row tile: a tile may cover the end of one image and the start of the next.  The same holds for every entry that takes
+ *   (cout, cout_pad, w, bias, da, za) below. */
 int qv2x_heads_f32(const float* x, int R, int hw, int cout, int cout_pad, const float* w, const float* bias,
                    const float* da, const float* za, float* out, void* stream);
 
