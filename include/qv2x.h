@@ -178,11 +178,20 @@ typedef struct {
     int32_t out_h, out_w;      /* interior size of the padded destination [n][out_h+2][out_w+2][out_ctotal]: must equal
                                 * (h*s, w*s), else QV2X_EINVAL (the reference's torch.cat raises on such a mismatch) */
 } qv2x_deconv_desc;
+/* Shape and alignment contract of the descriptor, checked on the host before any launch by all three entries (qv2x_deconv_i8,
+ * qv2x_deconv_i8_batch, qv2x_deconv_f32in; tests/test_deblock_layers_cpu.py):
+ *   QV2X_EINVAL: a null pointer; n, h, w < 1; s outside 1..8; out_delta not > 0; (out_h, out_w) != (h*s, w*s); out_c0 < 0 or
+ *                out_c0 + cout > out_ctotal; a batch of fewer than 1 or more than 4 layers.
+ *   QV2X_EALIGN: cin % 16, cout % 32 or s*s*cout % 64 not 0 (so s = 1 needs cout % 64 == 0); out_ctotal % 16 or out_c0 % 16 not 0
+ *                (16-byte stores); in, w, bias or out not 16-byte aligned.
+ * Only the interior of the destination's channel window [out_c0, out_c0 + cout) is written: its pad ring and every other channel
+ * keep their bytes. */
 int qv2x_deconv_i8(const qv2x_deconv_desc* desc /* host */, const int8_t* in, const float* w, const float* bias,
                    int8_t* out, void* stream);
 
 /* Up to 4 such layers in one launch (the deblocks only feed the concat: one pool of wave tiles instead of one tail per
- * layer).  Arrays of `n` host-side entries; results identical to `n` qv2x_deconv_i8 calls. */
+ * layer).  Arrays of `n` host-side entries, 1 <= n <= 4 (else QV2X_EINVAL), every layer under the contract above, any order,
+ * destinations equal or different; results identical to `n` qv2x_deconv_i8 calls. */
 int qv2x_deconv_i8_batch(const qv2x_deconv_desc* descs /* host */, int n, const int8_t* const* ins /* host array */,
                          const float* const* ws, const float* const* biases, int8_t* const* outs, void* stream);
 
@@ -541,7 +550,8 @@ int qv2x_conv3x3_i8_res(const qv2x_conv_desc* desc /* host */, const int8_t* in,
 
 /* qv2x_deconv_i8 on an fp32 map (QuantPyramidFusion's deblocks take the fused levels, quant_block.py:444-459; with s = 1 and the
  * weight transposed it is also conv1 of the first pyramid block, whose input is the decoded feature):  in f32 [N*H*W][cin]; the
- * descriptor's in_zx / in_delta are ignored; everything else as qv2x_deconv_i8. */
+ * descriptor's in_zx / in_delta are ignored; everything else as qv2x_deconv_i8, the descriptor's shape and alignment contract
+ * included (`in` 16-byte aligned; cin % 16 keeps every row of the map so). */
 int qv2x_deconv_f32in(const qv2x_deconv_desc* desc /* host */, const float* in, const float* w, const float* bias, int8_t* out, void* stream);
 
 /* UMGMQuantizer.decode (codebook.py:339-343) as table look-ups for any codebook width d (% 4): row r = (agent, cell),
