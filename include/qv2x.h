@@ -110,13 +110,27 @@ int qv2x_pfn_unscatter_i8(const int32_t* voxel_coords, int M, int value, int8_t*
  * QuantBaseBEVBackbone quant_block.py:243-303 and QuantDoubleConv :552-572), on integer codes:
  *     T_g  = sum_{kh,kw,ci in group g} (x - zx_g) * (w - zw[co])                  exact int32 (MFMA i8)
  *     y    = bias[co] + sum_g float(T_g) * scale[g][co]                           fp32 mul, add
- *     out  = clamp(rint(max(y, 0) / out_delta) + out_zp, 0, 255) - 128
+ *     out  = clamp(rint(fma(relu ? max(y, 0) : y, fl(1 / out_delta), out_zp)), 0, 255) - 128
+ *          -- ONE fused multiply-add with the fp32 reciprocal, rounded once to nearest even (csrc/common.h:q_pack4 and
+ *          oracle/qv2x_oracle.c:q_code_mul compute exactly this; the division form rint(y / out_delta) + out_zp differs from it near
+ *          rounding boundaries).  relu = 0 is the plain two-sided quantizer; relu != 0 clamps at out_zp from below.  out_zp is an
+ *          INTEGER in 0..255 passed as a float.
  *   in   : padded i8 BEV [N][H+2][W+2][cin_total]; input channel groups (the concat of the three deblocks
- *          carries three activation scales) described by group_c0/group_c/group_zx
+ *          carries three activation scales) described by group_c0/group_c/group_zx.  The groups may lie ANYWHERE in cin_total, in any
+ *          order, with gaps and spare channels around them (group_c % 64 == 0, group_c0 % 16 == 0, group_c0 + group_c <= cin_total);
+ *          w, scale and corr follow the descriptor's order.  Channels outside the groups are never read, the pad ring's included.
  *   w    : i8 (code - 128), [Cout][G][3][3][C_g]  (K contiguous per output channel)
  *   scale: f32 [G][Cout] = delta_x[g] * delta_w[co];  corr: i32 [G][Cout] = ax_g * sum_k ws + K_g * ax_g * aw[co]
  *          with ax_g = 128 - zx_g, aw[co] = 128 - zw[co], ws = w code - 128;  aw: i32 [Cout]; bias f32 [Cout]
- *   out  : padded i8 BEV [N][Ho+2][Wo+2][out_ctotal], written at channel offset out_c0 (interior only). */
+ *   out  : padded i8 BEV [N][Ho+2][Wo+2][out_ctotal], written at channel offset out_c0 (out_c0 % 16 == 0, out_ctotal % 16 == 0,
+ *          out_c0 + cout <= out_ctotal).  Only the interior of the channel window [out_c0, out_c0 + cout) is written: the pad ring and
+ *          every other channel keep their bytes.
+ * Exactness.  The kernels form T_g = sum xs*ws + aw * S + corr in int32, xs / ws = stored bytes, S = the sum of xs over the window
+ * (pad ring included).  They are specified while |T_g|, |sum xs*ws|, |aw * S| and |corr| stay below 2^31 and S fits 24 bits signed
+ * (|S| < 2^23: the single-group forms multiply with v_mul_i32_i24; 9 * group_c * 128 < 2^23 always holds below 7282 channels).  With
+ * codes and zero points anywhere in 0..255 that is 9 * group_c * 255^2 < 2^31, i.e. group_c <= 3669.  float(T_g) rounds to nearest even
+ * from |T_g| = 2^24 on, as the oracle's conversion does.  (tests/test_hip_conv_layers.py runs these bounds' neighbourhood: K = 9 * 1536 at
+ * codes and zero points of 0 and 255.) */
 typedef struct {
     int32_t n, h, w, cin_total, stride, cout;
     int32_t ngroups;
@@ -129,8 +143,12 @@ int qv2x_conv3x3_i8(const qv2x_conv_desc* desc /* host */, const int8_t* in, con
                     const float* scale, const int32_t* corr, const int32_t* aw, const float* bias,
                     int8_t* out, void* stream);
 
-/* The same convolution for wide layers (stride 1, cout % 256 == 0: the DoubleConv shrinker,
- * opencood/models/sub_modules/downsample_conv.py:17-31 under quant_block.py:552-572) with the weights pre-tiled:
+/* The same convolution with the weights pre-tiled, written for wide layers (the DoubleConv shrinker,
+ * opencood/models/sub_modules/downsample_conv.py:17-31 under quant_block.py:552-572).  qv2x_conv3x3_i8_wide ACCEPTS cout of 64, 128 or a
+ * multiple of 256 at stride 1 or 2 (several input groups only at stride 1 with cout % 256 == 0; at most 24 chunks of 64 input channels, 6
+ * at stride 2) and runs any accepted descriptor, whatever qv2x_conv3x3_i8_wide_ok says: _ok only answers whether the layer is large
+ * enough for this entry to pay.  Same descriptor contract as qv2x_conv3x3_i8 (relu, out_zp, groups anywhere in cin_total, the output
+ * window, the magnitude bounds):
  *   w_wide : i8 [Cout/T][chunk][tap][T/32][K half][lane][16], T = min(Cout, 256), chunk = the 64-channel chunks of group 0, then
  *            of group 1, ...: the MFMA A-operand fragments of a K step in load order (T x 64 bytes contiguous per K step, 1 KiB per
  *            wave-instruction); opaque to the caller, made from the row-major layout by qv2x_conv3x3_i8_pack_wide, once.
@@ -153,7 +171,9 @@ int qv2x_conv3x3_i8_wide(const qv2x_conv_desc* desc /* host */, const int8_t* in
  *   w_chain: i8 (code - 128) [depth][2][9][2][64][16]: the B fragments of v_mfma_i32_32x32x32_i8 in load order --
  *            [layer][cout / 32][tap][cin / 32][lane][16 B], lane = 32 * ((cin / 16) & 1) + cout % 32, bytes = cin % 16
  *   scale, bias f32 [depth][64]; corr, aw i32 [depth][64] (as qv2x_conv3x3_i8, one group);
- *   out_delta / out_zp: the output quantizer of every layer (the pad code of layer l's map is out_zp[l] - 128). */
+ *   out_delta / out_zp: the output quantizer of every layer (the pad code of layer l's map is out_zp[l] - 128): the requantizer of
+ *   qv2x_conv3x3_i8, out_zp[l] an integer in 0..255.  `relu` holds for every layer of the chain; relu = 0 is the two-sided quantizer.
+ *   Only the interior of `out` is written: its pad ring keeps its bytes. */
 typedef struct {
     int32_t n, h, w;           /* output map of every layer */
     int32_t in_h, in_w;        /* input map of layer 0 */

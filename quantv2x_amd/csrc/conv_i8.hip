@@ -14,7 +14,8 @@
 // (x - zx) = 0 there, which is exactly zero padding in the dequantized domain.
 //
 // Epilogue (spec shared with oracle/qv2x_oracle.c:orc_conv3x3): y = bias + sum_g float(T_g) * scale[g][co]
-// (separate mul and add), ReLU, requantize (q_code: equal to IEEE division + rint), store code - 128.
+// (separate mul and add), ReLU, requantize (q_pack4 / q_code_mul: clamp(rint(fma(y, fl(1 / delta), zp)), 0, 255), ONE fused multiply-add with
+// the fp32 reciprocal -- not the division form; the ReLU is folded into the lower clamp), store code - 128.
 // Wide stride-1 layers (cout % 256 == 0) have their own kernel and weight layout: conv_i8_wide.hip.
 #include <cstdlib>
 

@@ -18,7 +18,7 @@
 //   * the stride-2 first layer reads its input space-to-depth: four parity planes (row parity x column parity), so
 //     input (2r + dy, 2c + dx) is again a pure shift inside plane (dy & 1, dx & 1).
 //   * arithmetic is the single-group case of conv_i8.hip (exact i32 sums, zero-point correction from v_dot4 window sums,
-//     y = bias + float(T) * scale, ReLU, q_code): bit-identical to oracle/qv2x_oracle.c:orc_conv3x3 layer by layer.
+//     y = bias + float(T) * scale, ReLU, q_pack4 = clamp(rint(fma(y, fl(1 / delta), zp)), 0, 255)): bit-identical to oracle/qv2x_oracle.c:orc_conv3x3 layer by layer.
 #include "common.h"
 
 #ifndef QV2X_CHAIN_DBG
