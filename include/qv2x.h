@@ -40,7 +40,8 @@ const char* qv2x_last_error(void);
  * field (round 5; a caller built before it passes garbage there unless its struct was zero-initialised -- ADVICE r5); 6 = round 6:
  * qv2x_codebook_encode_candidates_i8 / qv2x_codebook_encode_listed_f32 added, no struct changed; 7 =
  * qv2x_codebook_encode_candidates_seg_i8 added and qv2x_codebook_encode_listed_f32 widened to seg_num 2 / dict_size 256, no struct changed;
- * 9 = qv2x_voxelize_batch_f32 / qv2x_postprocess_batch_f32 and their workspace queries added, no struct changed. */
+ * 9 = qv2x_voxelize_batch_f32 / qv2x_postprocess_batch_f32 and their workspace queries added, no struct changed.  The detection-evaluation
+ * entries (qv2x_eval_desc, qv2x_eval_workspace_bytes, qv2x_eval_tp_fp_f32) joined under 9: nothing that existed changed. */
 #define QV2X_ABI_VERSION 9
 int qv2x_version(void);            /* == QV2X_ABI_VERSION of the library's own build */
 
@@ -736,6 +737,44 @@ int qv2x_fuse_heads_band(const qv2x_fuse_desc* desc /* host */, int n_scenes, co
  * One launch; world * frames * cout <= 65535. */
 int qv2x_assemble_bands(const uint8_t* slabs, int world, int64_t slab_bytes, int frames, int cout, int h, int w, int wire,
                         const float* da, const float* za, float* out, void* stream);
+
+/* ---- detection evaluation: which detections are true / false positives, for a batch of frames and every problem at once ---------
+ * caluclate_tp_fp of the reference (opencood/utils/eval_utils.py:40-120; eval_utils_mc.py:41-93 is the same walk without the range
+ * filter) on the boxes the post-process entries write, without leaving the device.  A PROBLEM is one (class, range, threshold) triple of
+ * one frame; P = max(1, n_classes) * n_ranges * n_thresholds per frame, index (class * n_ranges + range) * n_thresholds + threshold.
+ *   order     the first det_count[f] rows of a frame in stable descending score order: equal scores keep the lower row first (as
+ *             nms_rotated; np.argsort(-score) of eval_utils.py:98 is unstable, its order among ties undefined).  The input need not be sorted.
+ *   centre    the sum of the four bottom-face corners in index order times 0.25, distance = sqrt(x^2 + y^2), in fp64 (the centroid of
+ *             eval_utils.py:80-93).  A detection or GT belongs to a problem iff its row is below the frame's count, its label equals the
+ *             problem's class (n_classes > 0; a label outside 1..n_classes belongs to none) and left < distance < right.
+ *   IoU       (float)(inter / union) with the fp64 convex clipping of the rotated NMS, union = area_a + area_b - inter, 0 when
+ *             union <= 0 or the bounding boxes are disjoint (common_utils.py:230-252 takes the areas from shapely).
+ *   matching  eval_utils.py:100-114: a problem's detections in rank order; among the problem's GT not yet matched the largest fp32 IoU, on
+ *             ties the lowest GT row; no GT left or that IoU < (float)threshold: false positive, else true positive and the GT is removed.
+ *   det_corners f32 [frames][det_cap][8][3] (the layout qv2x_postprocess_batch_f32 writes: x, y of corners 0..3 are read),
+ *   det_scores f32 [frames][det_cap], det_labels i32 [frames][det_cap], det_count i32 [frames]; gt_corners f32 [frames][gt_cap][8][3],
+ *   gt_labels i32 [frames][gt_cap], gt_count i32 [frames] (counts are clamped to 0..cap).  Labels are ignored and may be NULL with n_classes == 0.
+ *   out_order  i32 [frames][det_cap]     the row at rank r (-1 for r >= det_count[f]);  out_scores f32 [frames][det_cap]  its score (0 there)
+ *   out_flags  u8  [frames][P][det_cap]  per rank: 0 = not in this problem, 1 = false positive, 2 = true positive
+ *   out_match  i32 [frames][P][det_cap]  per rank: the matched GT row, or -1
+ *   out_gt     i32 [frames][P]           the number of the problem's GT
+ * All data pointers are device pointers; three launches, no host loop over frames or problems, nothing copied: HIP-graph capturable.
+ * workspace: qv2x_eval_workspace_bytes(desc) bytes, 256-byte aligned (-1: bad descriptor).  Non-finite scores or corners: undefined results. */
+typedef struct {
+    int32_t frames;          /* 1..64 */
+    int32_t det_cap;         /* 1..1024: rows per frame in the detection arrays */
+    int32_t gt_cap;          /* 1..256 */
+    int32_t n_classes;       /* 0 = class-agnostic (labels ignored, may be NULL); 1..4 = one problem set per label 1..n_classes */
+    int32_t n_ranges;        /* 1..4 */
+    int32_t n_thresholds;    /* 1..4, each in (0, 1] */
+    float ranges[4][2];      /* (left, right) in metres; -INFINITY / INFINITY allowed; membership is left < d < right (strict) */
+    float thresholds[4];
+} qv2x_eval_desc;
+int64_t qv2x_eval_workspace_bytes(const qv2x_eval_desc* desc /* host */);
+int qv2x_eval_tp_fp_f32(const qv2x_eval_desc* desc /* host */, const float* det_corners, const float* det_scores, const int32_t* det_labels,
+                        const int32_t* det_count, const float* gt_corners, const int32_t* gt_labels, const int32_t* gt_count,
+                        void* workspace, int64_t workspace_bytes, int32_t* out_order, float* out_scores, uint8_t* out_flags,
+                        int32_t* out_match, int32_t* out_gt, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
