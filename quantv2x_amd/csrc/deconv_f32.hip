@@ -154,13 +154,19 @@ __device__ __forceinline__ void deconv_tile(const DeconvArgs& a, const int tile,
 }
 
 // ---- round 5: the PIXEL-STATIONARY form for launches of many rounds of waves (a batch of frames) ---------------------------------------
-// On this part a wave's VALU instructions do not hide behind f32 MFMAs -- its own or its SIMD-mate's (the encode kernel's
-// stamps) -- so what the 64 x 64 form above loses is what it ISSUES beside them: five VALU per int8 -> fp32 conversion, every pixel
+// On this part a wave's VALU instructions do not hide behind its SIMD-mate's f32 MFMAs, and behind its own only while it has the SIMD
+// to itself (the encode kernel's stamps; measured on this kernel: the last paragraph below) -- so what the 64 x 64 form above loses is what it ISSUES beside them: five VALU per int8 -> fp32 conversion, every pixel
 // converted once per 64 columns (80 per 32 MFMAs = 15 % of a step), and the per-lane address arithmetic of ten loads per step.  Here a
 // wave keeps the fp32 B operands of its 32 pixels in K / 2 registers (the encode wave form's idea: codebook_encode_wave.hip) and streams
 // the weights of NP pairs of 32-column tiles past them: a pixel is converted once per 128 NP columns, the weight loads are buffer loads
 // with a SCALAR running offset (one 8-byte load per lane feeds two MFMAs; the same [Cin/4][cols][k0,k2,k1,k3] array as above), the two
 // tiles of a pair are two independent MFMA chains.  Same ascending-ci fma chain per output, same epilogue: bit-identical results.
+// A pair's epilogue stays BEHIND its K loop.  Woven into the next pair's K loop out of a second accumulator set (one half quad or one
+// swap + store behind every few MFMAs, bias through LDS, 251 registers, no scratch, bit-exact) the launch of 32 frames took 975.0 us against
+// 969.8 (medians of five alternating runs, spreads 4.3 | 6.2): the stamps show the K loops growing by what the epilogues lose (Cin 128:
+// 9-10k -> 10-20k ticks) -- with two waves per SIMD the mate's MFMAs hold the woven VALU back as they hold back an epilogue (finding 1).
+// With ONE workgroup per CU the woven K loops run at 1.13-1.2x their MFMA time and the epilogues vanish, but the item starts and the
+// tail stand exposed: 1133 us.  profiles/r10_deconv_woven.md has the numbers.
 constexpr int PS_NPF = 4;                     // weight quads in flight per tile
 
 #ifdef QV2X_DPS_FINE                          // dev build (tools/dps_fine.py): s_memtime stamps of every 36th item of every Cin
