@@ -41,7 +41,8 @@ const char* qv2x_last_error(void);
  * qv2x_codebook_encode_candidates_i8 / qv2x_codebook_encode_listed_f32 added, no struct changed; 7 =
  * qv2x_codebook_encode_candidates_seg_i8 added and qv2x_codebook_encode_listed_f32 widened to seg_num 2 / dict_size 256, no struct changed;
  * 9 = qv2x_voxelize_batch_f32 / qv2x_postprocess_batch_f32 and their workspace queries added, no struct changed.  The detection-evaluation
- * entries (qv2x_eval_desc, qv2x_eval_workspace_bytes, qv2x_eval_tp_fp_f32) joined under 9: nothing that existed changed. */
+ * entries (qv2x_eval_desc, qv2x_eval_workspace_bytes, qv2x_eval_tp_fp_f32) and the ground-truth entry (qv2x_gt_desc, qv2x_gt_boxes_f32)
+ * joined under 9: nothing that existed changed, and a caller that needs them finds out by looking the symbol up. */
 #define QV2X_ABI_VERSION 9
 int qv2x_version(void);            /* == QV2X_ABI_VERSION of the library's own build */
 
@@ -775,6 +776,50 @@ int qv2x_eval_tp_fp_f32(const qv2x_eval_desc* desc /* host */, const float* det_
                         const int32_t* det_count, const float* gt_corners, const int32_t* gt_labels, const int32_t* gt_count,
                         void* workspace, int64_t workspace_bytes, int32_t* out_order, float* out_scores, uint8_t* out_flags,
                         int32_t* out_match, int32_t* out_gt, void* stream);
+
+/* ---- ground-truth boxes: project, de-duplicate and range-mask the agents' object lists of a batch of frames ----------------------------
+ * generate_gt_bbx of the reference (opencood/data_utils/post_processor/base_postprocessor.py:47-107 single class,
+ * base_postprocessor_multi_class.py:46-103 multi-class) and generate_gt_bbx_by_iou (base_postprocessor.py:110-200), written directly in the
+ * layout qv2x_eval_tp_fp_f32 reads.  Row r = agent * obj_cap + slot of a frame; row order is the reference's concatenation order.
+ *   candidate  a row is a candidate iff agent < agent_counts[f] (clamped to 0..agents) and mask != 0.  Nothing else of a row that is no
+ *              candidate is looked at.
+ *   mode 0     a candidate survives iff no EARLIER candidate of the frame has the same id (any int32 value is an id).
+ *   mode 1     (agents <= 2; ids ignored, may be NULL) agent 0's candidates all survive; an agent-1 candidate survives iff its IoU with
+ *              every agent-0 candidate is <= (float)iou_threshold.  IoU = (float)(inter / union) on x, y of corners 0..3 of the PROJECTED
+ *              f32 boxes, with the fp64 convex clipping of the rotated NMS and of the evaluator (union <= 0 or disjoint bounding boxes: 0).
+ *   corners    from the f32 inputs in fp64: half extents times the template of box_utils.boxes_to_corners_3d (bottom face first: the corner
+ *              order the evaluator assumes), x' = x cos(yaw) - y sin(yaw), y' = x sin(yaw) + y cos(yaw), plus the centre, then
+ *              ((T[i][0] x + T[i][1] y) + T[i][2] z) + T[i][3] for rows 0..2 of the agent's 4x4 transform; rounded to f32 once.
+ *              order 0 ('hwl'): a row is x, y, z, h, w, l, yaw; order 1 ('lwh'): x, y, z, l, w, h, yaw; with row_floats 8 the label follows.
+ *   range      only a SURVIVOR's own box is range-masked, after the de-duplication (the reference's order: an id whose first occurrence
+ *              lies out of range is dropped even when a later agent's copy of it is in range).  A box qualifies iff all 8 corners satisfy
+ *              range[i] <= c[i] <= range[3 + i] on the f32 values, for x, y, z or, with range_xy_only, for x and y.
+ *   output     the qualifying survivors in candidate order (first occurrence first).  THIS ORDER IS THIS PROJECT'S CONTRACT: the
+ *              reference's own order comes from iterating a set() of ids and is arbitrary.  gt_totals[f] = rows that qualified,
+ *              gt_counts[f] = min(gt_totals[f], gt_cap) = rows written: a caller sees overflow as total > count without a synchronisation.
+ *              Rows past gt_counts[f] are left untouched.
+ *   boxes f32 [frames][agents][obj_cap][row_floats], mask u8 [frames][agents][obj_cap], ids i32 [frames][agents][obj_cap] (slot-aligned
+ *   with boxes), transforms f32 [frames][agents][4][4] (agent -> ego, row-major), agent_counts i32 [frames].
+ *   gt_corners f32 [frames][gt_cap][8][3]; gt_labels i32 [frames][gt_cap] = (int32)row[7] (required with row_floats 8, ignored with 7);
+ *   gt_ids i32 [frames][gt_cap] (may be NULL): the survivor's id in mode 0, its row r in mode 1; gt_counts, gt_totals i32 [frames].
+ * All data pointers are device pointers.  One launch whatever the batch (one workgroup per frame), nothing copied, no atomics: HIP-graph
+ * capturable.  QV2X_EINVAL before any GPU call for a null required pointer or a descriptor outside the limits below.  Non-finite inputs:
+ * undefined results (a NaN corner fails the range test). */
+typedef struct {
+    int32_t frames;          /* 1..64 */
+    int32_t agents;          /* 1..8 (mode 1: 1..2) */
+    int32_t obj_cap;         /* 1..256 rows per agent */
+    int32_t gt_cap;          /* 1..256: rows per frame in the outputs (the evaluator's gt_cap) */
+    int32_t row_floats;      /* 7, or 8 when the last column is the label */
+    int32_t order;           /* 0 = 'hwl', 1 = 'lwh' */
+    int32_t mode;            /* 0 = de-duplicate by id, 1 = by IoU */
+    int32_t range_xy_only;   /* 0 = x, y and z; 1 = x and y */
+    float range[6];          /* xmin, ymin, zmin, xmax, ymax, zmax */
+    float iou_threshold;     /* mode 1: in [0, 1] (the reference: 0.05) */
+} qv2x_gt_desc;
+int qv2x_gt_boxes_f32(const qv2x_gt_desc* desc /* host */, const float* boxes, const uint8_t* mask, const int32_t* ids, const float* transforms,
+                      const int32_t* agent_counts, float* gt_corners, int32_t* gt_labels, int32_t* gt_ids, int32_t* gt_counts,
+                      int32_t* gt_totals, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

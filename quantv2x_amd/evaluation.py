@@ -115,6 +115,13 @@ class DetectionEvaluator:
                 num_classes=self.num_classes)
             self._parts.append((scores, flags, gt))
 
+    def update_from(self, out: dict, gt: dict):
+        """``update`` on what ``ground_truth.gpu_gt_boxes_batch`` / ``GroundTruthAssembler`` return (``corners`` / ``labels`` / ``counts`` on the
+        device): nothing is read back in between.  A frame whose ``totals`` exceed its ``counts`` is evaluated on the rows that were written."""
+        if self.num_classes > 0 and gt.get("labels") is None:
+            raise ValueError("num_classes > 0 needs ground-truth labels (8-float object rows)")
+        self.update(out, gt["corners"], gt.get("labels"), gt["counts"])
+
     def result(self) -> dict:
         """-> ``ap`` f64, ``tp`` / ``fp`` / ``gt`` i64 arrays [classes, ranges, thresholds] (classes = max(1, num_classes)) and ``mrec`` /
         ``mpre``: nested lists of the same shape holding the curves.  A problem without GT reports ``ap`` nan and empty curves (the

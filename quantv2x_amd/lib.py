@@ -28,7 +28,7 @@ SYMBOLS = [
     "qv2x_codebook_encode_collapsed_f32", "qv2x_codebook_encode_candidates_i8", "qv2x_codebook_encode_candidates_seg_i8", "qv2x_codebook_encode_listed_f32", "qv2x_mean_vfe_f32", "qv2x_sp_index_scatter", "qv2x_sp_out_sites_workspace_bytes", "qv2x_sp_out_sites", "qv2x_sp_rulebook", "qv2x_sp_conv_f32in", "qv2x_sp_conv_i8", "qv2x_sp_to_bev_i8",
     "qv2x_fuse_att_band_f32", "qv2x_heads_band", "qv2x_fuse_heads_band", "qv2x_assemble_bands",
     "qv2x_voxelize_batch_workspace_bytes", "qv2x_voxelize_batch_f32", "qv2x_postprocess_batch_workspace_bytes", "qv2x_postprocess_batch_f32",
-    "qv2x_eval_workspace_bytes", "qv2x_eval_tp_fp_f32",
+    "qv2x_eval_workspace_bytes", "qv2x_eval_tp_fp_f32", "qv2x_gt_boxes_f32",
 ]
 WIRES = {"f32": 0, "u8": 1}     # QV2X_WIRE_F32, QV2X_WIRE_U8
 COMM_ID_BYTES = 128
@@ -120,6 +120,11 @@ class EvalDesc(C.Structure):
                 ("n_thresholds", C.c_int32), ("ranges", (C.c_float * 2) * 4), ("thresholds", C.c_float * 4)]
 
 
+class GtDesc(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("agents", C.c_int32), ("obj_cap", C.c_int32), ("gt_cap", C.c_int32), ("row_floats", C.c_int32),
+                ("order", C.c_int32), ("mode", C.c_int32), ("range_xy_only", C.c_int32), ("range", C.c_float * 6), ("iou_threshold", C.c_float)]
+
+
 class Qv2xError(RuntimeError):
     pass
 
@@ -198,6 +203,7 @@ def load() -> C.CDLL:
     lib.qv2x_eval_workspace_bytes.argtypes = [C.POINTER(EvalDesc)]
     lib.qv2x_eval_workspace_bytes.restype = C.c_int64
     lib.qv2x_eval_tp_fp_f32.argtypes = [C.POINTER(EvalDesc), vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    lib.qv2x_gt_boxes_f32.argtypes = [C.POINTER(GtDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.qv2x_postprocess_workspace_bytes.argtypes = [C.POINTER(PostprocessDesc)]
     lib.qv2x_postprocess_workspace_bytes.restype = C.c_int64
     lib.qv2x_postprocess_f32.argtypes = [C.POINTER(PostprocessDesc), vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp]

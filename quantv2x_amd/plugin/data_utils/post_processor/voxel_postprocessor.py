@@ -6,6 +6,11 @@ work done by ``qv2x_postprocess_f32`` (``csrc/postprocess.hip``).  Training-side
 ``post_process`` handles what intermediate / early fusion produces (``output_dict`` with the ego entry only) and late fusion (one
 entry per CAV: ``qv2x_postprocess_late_f32``, up to 8 CAVs).  The head maps must live on the GPU (they come from ``DeployedModel``);
 there is no CPU fallback.
+
+``generate_gt_bbx`` (base_postprocessor.py:47-107) and ``generate_gt_bbx_by_iou`` (:110-200) run ``qv2x_gt_boxes_f32`` (``csrc/gt_boxes.hip``)
+as a batch of one and read back, because the reference's callers expect a sized tensor; ``quantv2x_amd.ground_truth`` is the batched surface
+that reads nothing back.  ``gt_boxes_frame`` below is the numpy statement of that entry's contract (include/qv2x.h), the way
+``eval_utils.tp_fp_frame`` states the evaluator's: fp64 with one rounding, the CPU and GPU tests compare against it.
 """
 import ctypes as C
 import math
@@ -136,6 +141,81 @@ def gpu_post_process_batch(owner, cls, reg, dirp, anchors_dev, transformation_ma
     return corners, scores, labels, counts
 
 
+# ---- ground truth: the numpy statement of qv2x_gt_boxes_f32 -----------------------------------------------------------------------------
+_TEMPLATE = np.array([[1, -1, -1], [1, 1, -1], [-1, 1, -1], [-1, -1, -1], [1, -1, 1], [1, 1, 1], [-1, 1, 1], [-1, -1, 1]], np.float64)
+GT_ORDERS = {"hwl": 0, "lwh": 1}
+
+
+def gt_project_boxes(rows, transform, order):
+    """f32 box rows [N, >= 7] (``order`` 'hwl': x, y, z, h, w, l, yaw; 'lwh': x, y, z, l, w, h, yaw) and a 4x4 transform -> f32 [N, 8, 3]:
+    ``boxes_to_corners_3d`` + ``project_box3d`` (box_utils.py:152-204, :278-316) from the f32 inputs in float64, rounded once; the sums in
+    the order include/qv2x.h states."""
+    b = np.asarray(rows, np.float32).astype(np.float64).reshape(-1, np.shape(rows)[-1])
+    t = np.asarray(transform, np.float32).astype(np.float64)
+    lwh = b[:, [5, 4, 3]] if GT_ORDERS[order] == 0 else b[:, 3:6]
+    p = (0.5 * lwh)[:, None, :] * _TEMPLATE[None]                   # [N, 8, 3]
+    cs, sn = np.cos(b[:, 6])[:, None], np.sin(b[:, 6])[:, None]
+    x = (p[..., 0] * cs - p[..., 1] * sn) + b[:, None, 0]
+    y = (p[..., 0] * sn + p[..., 1] * cs) + b[:, None, 1]
+    z = p[..., 2] + b[:, None, 2]
+    return np.stack([((t[i, 0] * x + t[i, 1] * y) + t[i, 2] * z) + t[i, 3] for i in range(3)], axis=-1).astype(np.float32)
+
+
+def gt_boxes_frame(boxes, mask, ids, transforms, *, order, mode, gt_range, range_xy_only, iou_threshold=0.05):
+    """One frame of ``qv2x_gt_boxes_f32`` in numpy.  ``boxes`` f32 [agents, obj_cap, 7 or 8], ``mask`` [agents, obj_cap], ``ids`` i32
+    [agents, obj_cap] (None in mode 1), ``transforms`` [agents, 4, 4]: the agents in use only.  Candidates are the rows with their mask set, in
+    (agent, slot) order; mode 0 keeps a candidate iff no earlier candidate has its id, mode 1 keeps agent 0's and those of agent 1 whose
+    ``float32(inter / union)`` with every candidate of agent 0 is ``<= float32(iou_threshold)`` (bottom faces of the projected f32 boxes,
+    ``eval_utils.iou_matrix``); then the survivor's own f32 corners are range-masked (``>=`` / ``<=`` against the f32 bounds, all 8 corners,
+    x and y or x, y and z).  -> dict: ``corners`` f32 [N, 8, 3], ``labels`` i32 [N] (None for 7-float rows), ``ids`` i32 [N] (mode 1: the row
+    agent * obj_cap + slot), ``rows`` i64 [N], in candidate order, uncapped."""
+    from ...utils.eval_utils import iou_matrix
+    boxes = np.asarray(boxes, np.float32)
+    agents, cap, width = boxes.shape
+    if mode == 1 and agents > 2:
+        raise ValueError("mode 1 takes at most 2 agents")
+    cand = np.nonzero(np.asarray(mask).reshape(-1) != 0)[0]           # rows agent * obj_cap + slot, ascending
+    if agents == 0 or cand.size == 0:
+        corners = np.zeros((0, 8, 3), np.float32)
+    else:
+        corners = np.concatenate([gt_project_boxes(boxes[a][cand[cand // cap == a] % cap], np.asarray(transforms)[a], order) for a in range(agents)])
+    if mode == 0:
+        flat = np.asarray(ids, np.int32).reshape(-1)[cand]
+        seen, keep = set(), np.zeros((cand.size,), bool)
+        for k, v in enumerate(flat.tolist()):
+            keep[k] = v not in seen
+            seen.add(v)
+    else:
+        first = cand // cap == 0
+        keep = first.copy()
+        q = corners[:, :4, :2].astype(np.float64)
+        iou = iou_matrix(q[~first], q[first])
+        keep[~first] = ~(iou > np.float32(iou_threshold)).any(axis=1)
+        flat = cand.astype(np.int32)
+    rng = np.asarray(gt_range, np.float32)
+    dims = 2 if range_xy_only else 3
+    inside = ((corners[..., :dims] >= rng[:dims]) & (corners[..., :dims] <= rng[3:3 + dims])).all(axis=(1, 2))
+    keep &= inside
+    return {"corners": corners[keep], "labels": boxes.reshape(-1, width)[cand[keep], 7].astype(np.int32) if width == 8 else None,
+            "ids": flat[keep].astype(np.int32), "rows": cand[keep]}
+
+
+def _gt_from_data_dict(owner, data_dict, by_iou=False):
+    """the reference-named methods: one frame through ``quantv2x_amd.ground_truth`` on the GPU, read back to a sized result
+    -> (corners [N, 8, 3], labels i32 [N] or None)"""
+    from ....ground_truth import MAX_GT, MAX_OBJ, GroundTruthAssembler
+    n = max(1, len(data_dict))
+    cap = min(MAX_OBJ, max([1] + [int(np.shape(c["object_bbx_center"])[0]) for c in data_dict.values()]))
+    key = (n, cap, by_iou)
+    if getattr(owner, "_gt_asm", None) is None or owner._gt_asm[0] != key:
+        owner._gt_asm = (key, GroundTruthAssembler(owner, max_agents=n, obj_cap=cap, gt_cap=MAX_GT, frames=1, by_iou=by_iou))
+    out = owner._gt_asm[1].fill([data_dict])()
+    count, total = (int(v) for v in torch.stack([out["counts"][0], out["totals"][0]]).tolist())    # the one host synchronisation (the reference goes to numpy here)
+    if total > count:
+        raise RuntimeError(f"{total} ground-truth boxes in one frame: the evaluator's layout holds {count}")
+    return out["corners"][0, :count].clone(), (out["labels"][0, :count].clone() if out["labels"] is not None else None)
+
+
 class VoxelPostprocessor:
     def __init__(self, anchor_params, train):
         self.params = anchor_params
@@ -205,3 +285,16 @@ class VoxelPostprocessor:
             dir_offset=float(self.params["dir_args"]["dir_offset"]) if has_dir else 0.0,
             rng=self.params["gt_range"], range_xy_only=False, max_extent=6.0, z_lim=(-3.0, 1.0), max_boxes=max_boxes)
         return boxes, scores
+
+    # ---- ground truth ----------------------------------------------------------------------------------------
+    def generate_gt_bbx(self, data_dict):
+        """-> gt_box3d_tensor [N, 8, 3] on the GPU: the CAVs' boxes projected with ``transformation_matrix_clean``, de-duplicated by object
+        id (first occurrence, in that order: the reference's order is a ``set()``'s) and masked to ``gt_range`` on x, y and z."""
+        return _gt_from_data_dict(self, data_dict)[0]
+
+    def generate_gt_bbx_by_iou(self, data_dict):
+        """-> gt_box3d_tensor [N, 8, 3] on the GPU (DAIR-V2X late fusion: two label sources, no ids): the second source's boxes whose BEV IoU
+        with a box of the first exceeds 0.05 are dropped, then the mask to ``gt_range`` on x and y."""
+        if len(data_dict) > 2:
+            raise NotImplementedError("generate_gt_bbx_by_iou: one or two label sources")
+        return _gt_from_data_dict(self, data_dict, by_iou=True)[0]

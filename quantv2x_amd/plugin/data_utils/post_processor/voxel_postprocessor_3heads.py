@@ -2,11 +2,12 @@
 (the V2X-Real multi-class yaml): constructor, ``generate_anchor_box`` (:63-132) and
 ``post_process(data_dict, output_dict, projection=True)`` (:318-478) -> ``(pred_box3d_tensor [K, 8, 3],
 score_labels [K, 2])``, the work done by ``qv2x_postprocess_f32`` with ``num_classes > 1``.
-Training-side members are out of scope."""
+``generate_gt_bbx`` (base_postprocessor_multi_class.py:46-103) -> ``(gt_box3d_tensor [N, 8, 3], gt_label_tensor [N])`` runs
+``qv2x_gt_boxes_f32`` as a batch of one.  Training-side members are out of scope."""
 import numpy as np
 import torch
 
-from .voxel_postprocessor import gpu_post_process
+from .voxel_postprocessor import _gt_from_data_dict, gpu_post_process
 
 # opencood/data_utils/datasets/__init__.py:25 -- the module constant box_utils_mc.get_mask_for_boxes_within_range_torch reads
 GT_RANGE = [-100, -40, -15, 100, 40, 15]
@@ -99,3 +100,9 @@ class VoxelPostprocessor3Heads:
         if boxes is None:
             return None, None
         return boxes, torch.cat([scores.unsqueeze(1), labels.to(torch.float32).unsqueeze(1)], dim=1)
+
+    def generate_gt_bbx(self, data_dict):
+        """-> (gt_box3d_tensor [N, 8, 3], gt_label_tensor f32 [N]) on the GPU: the CAVs' 8-float rows (label last) projected with
+        ``transformation_matrix``, de-duplicated by object id (first occurrence, in that order) and masked to ``GT_RANGE`` on x and y."""
+        boxes, labels = _gt_from_data_dict(self, data_dict)
+        return boxes, labels.to(torch.float32)
