@@ -2,8 +2,9 @@
 // builds the reference's pairwise matrix from them:
 //     pairwise[i][j] = T_j^-1 T_i = solve(T_j, T_i)        get_pairwise_transformation, opencood/utils/transformation_utils.py:21-66
 // identity for i == j and for the padding rows / columns up to max_cav.  One thread per (i, j); float64 Gaussian elimination
-// with partial pivoting in a fixed operation order (separate multiply and subtract): bit-identical to oracle/geometry.py:solve4.
+// with partial pivoting in a fixed operation order (separate multiply and subtract, solve4.h): bit-identical to oracle/geometry.py:solve4.
 #include "common.h"
+#include "solve4.h"
 
 namespace qv2x {
 
@@ -24,37 +25,7 @@ __global__ void pairwise_from_poses_kernel(const uint8_t* __restrict__ gathered,
     const double* pi = (const double*)(gathered + (size_t)i * agent_stride + pose_offset);
     for (int r = 0; r < 4; ++r)
         for (int c = 0; c < 4; ++c) { a[r][c] = pj[r * 4 + c]; b[r][c] = pi[r * 4 + c]; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int p = k;
-#pragma unroll
-        for (int r = k + 1; r < 4; ++r)
-            if (fabs(a[r][k]) > fabs(a[p][k])) p = r;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const double ta = a[k][c], tb = b[k][c];
-#pragma unroll
-            for (int r = k + 1; r < 4; ++r)
-                if (r == p) { a[k][c] = a[r][c]; a[r][c] = ta; b[k][c] = b[r][c]; b[r][c] = tb; }
-        }
-#pragma unroll
-        for (int r = k + 1; r < 4; ++r) {
-            const double m = a[r][k] / a[k][k];
-#pragma unroll
-            for (int c = k + 1; c < 4; ++c) a[r][c] = a[r][c] - m * a[k][c];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) b[r][c] = b[r][c] - m * b[k][c];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 3; r >= 0; --r) {
-            double s = b[r][c];
-#pragma unroll
-            for (int q = r + 1; q < 4; ++q) s = s - a[r][q] * x[q][c];
-            x[r][c] = s / a[r][r];
-        }
+    solve4(a, b, x);
     for (int r = 0; r < 4; ++r)
         for (int c = 0; c < 4; ++c) o[r * 4 + c] = x[r][c];
 }

@@ -1,5 +1,5 @@
 """Pose helpers on the hot path; mirror of ``opencood/utils/transformation_utils.py``
-(``normalize_pairwise_tfm :68-92``, ``get_pairwise_transformation :21-66``, ``x_to_world :264-310``)."""
+(``normalize_pairwise_tfm :68-92``, ``get_pairwise_transformation :21-66``, ``x_to_world :264-310``, ``x1_to_x2 :310-334``)."""
 import numpy as np
 
 
@@ -27,6 +27,11 @@ def x_to_world(pose):
         [sy * cp, sy * sp * sr + cy * cr, -sy * sp * cr + cy * sr, y],
         [sp, -cp * sr, cp * cr, z],
         [0.0, 0.0, 0.0, 1.0]])
+
+
+def x1_to_x2(x1, x2):
+    """Poses ``x1``, ``x2`` ([x, y, z, roll, yaw, pitch], degrees, world frame) -> 4x4 T_x2_x1, the reference's way: ``inv`` then ``dot``."""
+    return np.dot(np.linalg.inv(x_to_world(x2)), x_to_world(x1))
 
 
 def get_pairwise_transformation(base_data_dict, max_cav, proj_first):
