@@ -19,7 +19,7 @@ There is no CPU / eager fallback here: if ``libqv2x.so`` is missing, constructio
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -242,6 +242,18 @@ class _Heads:
             off = bool(state[n + "/a_off"])
             das.append(np.full(w.shape[0], -1.0 if off else float(np.float32(state[n + "/a_delta"])), np.float32))
             zas.append(np.full(w.shape[0], 0.0 if off else float(state[n + "/a_zp"]), np.float32))   # (a disabled quantizer's parameters are never read)
+        self._stack(ws, bs, das, zas, dev)
+
+    @classmethod
+    def folded_fp32(cls, state, suffix, dev):
+        """the heads of an un-quantized model (``<head>/w`` [C, 256], ``<head>/bias``): every output quantizer off"""
+        hd = cls.__new__(cls)
+        ws = [state[h + suffix + "/w"] for h in _HEADS]
+        hd._stack(ws, [state[h + suffix + "/bias"] for h in _HEADS], [np.full(w.shape[0], -1.0, np.float32) for w in ws],
+                  [np.zeros(w.shape[0], np.float32) for w in ws], dev)
+        return hd
+
+    def _stack(self, ws, bs, das, zas, dev):
         self.splits = [w.shape[0] for w in ws]
         self.cout = sum(self.splits)
         self.cout_pad = (self.cout + 31) // 32 * 32
@@ -348,8 +360,120 @@ def assemble_heter_codes(owner: str, engines: dict, slot_cache: dict, agents: li
     return enc
 
 
-class DeployedModel(nn.Module):
-    """The hot path as HIP kernels.  Same call contract as the reference's model."""
+def pillar_inputs(inputs: dict, pfn: bool = True):
+    """``(voxel_features, voxel_coords i32, voxel_num_points i32)`` of one ``inputs_m1`` dict, contiguous, as the PFN kernels take them
+    (``pfn=False``: the SECOND encoder, which states its own voxel shape)."""
+    vf = inputs["voxel_features"].contiguous()
+    co = inputs["voxel_coords"].to(torch.int32).contiguous()
+    npnt = inputs["voxel_num_points"].to(torch.int32).contiguous()
+    if pfn and (vf.dtype != torch.float32 or vf.dim() != 3 or tuple(vf.shape[1:]) != (32, 4)):
+        raise ValueError("voxel_features must be float32 [M, 32, 4]")
+    return vf, co, npnt
+
+
+def pfn_params(state: Dict[str, np.ndarray]):
+    """a1 of a W8A8 state: ``(L.PfnParams, (delta, zero point) of the canvas)`` -- the host struct qv2x_pfn_scatter_i8 takes by value."""
+    s, n = state, "encoder_m1.pillar_vfe.pfn_layers.0.linear"
+    wq = ((s[n + "/w_code"].astype(np.float32) - s[n + "/w_zp"].astype(np.float32)[:, None])
+          * s[n + "/w_delta"].astype(np.float32)[:, None]).astype(np.float32)
+    if wq.shape != (64, 10):
+        raise NotImplementedError("deployed PFN expects Linear(10 -> 64)")
+    p = L.PfnParams()
+    p.w[:] = wq.reshape(-1).tolist()
+    p.b[:] = s[n + "/bias"].astype(np.float32).tolist()
+    p.d1, p.z1 = float(np.float32(s[n + "/a_delta"])), float(s[n + "/a_zp"])
+    p.d2, p.z2 = float(np.float32(s["pfn/a2_delta"])), float(s["pfn/a2_zp"])
+    p.vox[:] = [float(np.float32(v)) for v in s["meta/voxel"]]
+    p.off[:] = [float(np.float32(v)) for v in s["meta/offset"]]
+    return p, (p.d2, int(p.z2))
+
+
+def level_blob_host(state: Dict[str, np.ndarray], l: int, ke: int, D: int, segs: int):
+    """One codebook level's heads as the flat fp32 blob the encode kernels read (codebook_encode.h, include/qv2x.h) ->
+    ``(flat, cb_off, c2_off)``: the offsets, in floats, of the row-major codebook and of its ``c2`` slot (``ke`` zeros; filled on the device).
+    ``D == 64`` is the native 64-wide layout (qv2x_codebook_encode64_f32); every other ``D <= 256`` is zero-padded to the 256-wide one, which
+    carries the wave form's section too (every extra term of every fma chain is 0 * 0 and the padded |.|^2 chains are exactly 0, so the
+    codes equal a native evaluation bit for bit).  The last level (no ``lhead_w``) has an all-zero lhead."""
+    W = 64 if D == 64 else 256
+    last = f"codebook/{l}/lhead_w" not in state
+
+    def padded(n, *shape):
+        out = np.zeros(shape, np.float32)
+        if not (last and n.startswith("lhead")):
+            a = state[f"codebook/{l}/{n}"]
+            out[tuple(slice(0, k) for k in a.shape)] = a
+        return out
+    stage, qhead, lhead, cb = padded("stage_w", W, W), padded("qhead_w", W, W), padded("lhead_w", W, W), padded("codebook", ke, W)
+    parts = [_pack_k4p(stage), padded("stage_b", W), _pack_k4p(qhead), padded("qhead_b", W), _pack_k4p(lhead), padded("lhead_b", W),
+             _pack_k4p(cb), cb, np.zeros(ke, np.float32)]
+    flat = np.concatenate([p.reshape(-1) for p in parts])
+    c2_off = flat.size - ke                                          # the workgroup form's section ends with c2
+    if W == 256:
+        flat = np.concatenate([flat, wave_section(stage, qhead, lhead, cb, segs)])
+    return flat, c2_off - ke * W, c2_off
+
+
+def level_blob(lib, state: Dict[str, np.ndarray], l: int, ke: int, D: int, segs: int, dev) -> torch.Tensor:
+    """``level_blob_host`` on the device, its ``c2`` slot filled by the matching qv2x_codebook[64]_c2_f32"""
+    flat, cb_off, c2_off = level_blob_host(state, l, ke, D, segs)
+    floats, c2fn, name = ((lib.qv2x_codebook64_level_floats, lib.qv2x_codebook64_c2_f32, "qv2x_codebook64_c2_f32") if D == 64
+                          else (lib.qv2x_codebook_level_floats, lib.qv2x_codebook_c2_f32, "qv2x_codebook_c2_f32"))
+    assert flat.size == floats(ke)
+    blob = _dev(flat, dev)
+    L.check(c2fn(C.c_void_p(blob.data_ptr() + 4 * cb_off), ke, C.c_void_p(blob.data_ptr() + 4 * c2_off), L.current_stream()), name)
+    return blob
+
+
+class CodebookConstants(NamedTuple):
+    enc_levels: int                     # residual levels: what the encode kernels count
+    segs: int
+    levels: int                         # code planes = enc_levels * segs: what everything downstream of the encode counts
+    ke: int                             # rows of the extended codebook = segs * kc
+    kc: int
+    D: int
+    lut_host: np.ndarray                # the decode table [levels][kc][D] and its bias [D]
+    lut_bias_host: np.ndarray
+    lut: torch.Tensor
+    lut_bias: torch.Tensor
+    level_blobs: List[torch.Tensor]
+    level_ptrs: object                  # (C.c_void_p * enc_levels) of the blobs
+
+
+def codebook_constants(lib, state: Dict[str, np.ndarray], dev, refuse) -> CodebookConstants:
+    """a6 / a7 of every engine.  seg_num (m) > 1: the state holds the EXTENDED codebook [m * kc][D] (ptq_state.extended_codebook).  Downstream
+    of the encode everything counts code PLANES: ``levels`` = residual levels * m (the wire's [levels][agents][H*W] planes and the decode
+    table [levels][kc][D], which is the per-level table over the extended rows read plane by plane); the encode kernels get the true level
+    count ``enc_levels`` and ``segs``.  ``refuse(ke, kc, D, segs)`` raises for what the calling engine's kernels do not take, before any upload."""
+    s = state
+    enc_levels, segs = int(s["meta/codebook_levels"]), int(s.get("meta/codebook_segs", 1))
+    ke, D = (int(v) for v in s["codebook/0/codebook"].shape)
+    kc, levels = ke // segs, enc_levels * segs
+    refuse(ke, kc, D, segs)
+    lut, lut_bias = decode_tables(s, enc_levels, D)
+    lut = lut.reshape(levels, kc, D)
+    blobs = [level_blob(lib, s, l, ke, D, segs, dev) for l in range(enc_levels)]
+    return CodebookConstants(enc_levels, segs, levels, ke, kc, D, lut, lut_bias, _dev(lut, dev), _dev(lut_bias, dev), blobs,
+                             (C.c_void_p * enc_levels)(*[b.data_ptr() for b in blobs]))
+
+
+def _pairwise_from_poses(self, gathered: torch.Tensor, world: int, agent_stride: int, pose_offset: int, max_cav: int, out: torch.Tensor):
+    """pairwise f64 [max_cav, max_cav, 4, 4] from the poses inside the gathered payloads (qv2x_pairwise_from_poses_f64): the method of that
+    name of every engine with the multi-GPU stage interface (it reads ``self.lib`` only)."""
+    L.check(self.lib.qv2x_pairwise_from_poses_f64(L.ptr(gathered), world, agent_stride, pose_offset, max_cav, L.ptr(out),
+                                                  L.current_stream()), "qv2x_pairwise_from_poses_f64")
+
+
+class DeployedPostStage(nn.Module):
+    """What every engine of the AttFusion / MaxFusion network shares: the codebook constants and the POST stage a7-a11 on the agents' wire
+    data (decode + warp + fusion, the heads, the ``*_single`` heads), the reference's model contract around it (``forward`` = ``encode_agents``
+    + ``finish``), HIP-graph capture and the multi-GPU stage interface (dist.py).  The code planes are the boundary (``DeployedHeterModel``).
+
+    An agent stage (a1-a6: ``DeployedModel`` in W8A8, ``DeployedFp32Model`` in fp32) derives from it, calls ``_set_heads`` and provides
+      ``_workspace(n)``               the buffers of ``n`` agents; the first one sets the feature map's size ``fh``, ``fw``
+      ``heads``, ``heads_single``     (through ``_set_heads``)
+      ``encode_agents(inputs, n, taps)``  the wire data of ``n`` agents: code planes u8 [levels, n, H*W], or the shrinker output without a codebook
+      ``encode_into(inputs, frames, codes_out)``  the same for ``frames`` frames of one agent, into the caller's payload
+      ``_shared_features(enc, n)``    without a codebook: that shrinker output as fp32 rows [n, H*W, 256]"""
     # a7-a11 as ONE launch (qv2x_fuse_heads_batch_f32: the fused map stays in LDS) from this many 32-cell tiles on -- four rounds of the
     # chip's 1280 resident workgroups; below it (one frame: a single round) the two launches are faster.  Measured at a batch of 32
     # V2X-Real frames: round 4 (the agent-by-agent walk inside the tile kernel, profiles/r04_fuse_heads_times.log): single-agent scenes 1160
@@ -358,15 +482,421 @@ class DeployedModel(nn.Module):
     # 1428 + 629; of five / eight (the eight-agent instantiation: 140 registers) 2889 against 2450 / 3790 against 3156 -- up to FOUR agents.
     fuse_heads_min_tiles = 4 * 1280
     fuse_heads_max_agents = 4           # (with three code planes: the batched form needs them; otherwise scenes of one agent -- _one_launch_agents)
-    # scenes of ONE agent: every head by table look-up on the agent's own codes (qv2x_table_heads_f32; see __init__)
+    # scenes of ONE agent: every head by table look-up on the agent's own codes (qv2x_table_heads_f32; see _set_heads)
     single_agent_tables = True
     band_one_launch = None              # the band path's form: None = by the agent count (as _post_form); True / False force it (tests, tools/bench_band_post.py)
     _band_rows = None
-    table_heads = None                                                   # (engines that build their own heads -- the fp32 ones -- keep the general path)
+
+    def __init__(self, state: Dict[str, np.ndarray], device, emit_single_preds: Optional[bool]):
+        super().__init__()
+        self.lib = L.load()                      # raises if libqv2x.so is absent: no fallback
+        if not torch.cuda.is_available():
+            raise L.Qv2xError(f"{type(self).__name__} needs an MI355X (torch.cuda.is_available() is False)")
+        self.state, self.dev = state, torch.device(device)
+        s, dev = state, self.dev
+        if str(s.get("meta/fusion_method", "att")) not in ("att", "max"):
+            raise NotImplementedError(f"deployed path: fusion_method {s['meta/fusion_method']!r} ('att' = AttFusion and 'max' = MaxFusion are built here)")
+        self.fusion = 1 if str(s.get("meta/fusion_method", "att")) == "max" else 0
+        self.nx, self.ny, _ = (int(v) for v in s["meta/grid"])
+        self.hm, self.wm = (float(v) for v in s["meta/HW_metres"])
+        self.ratio = float(s["meta/discrete_ratio"])
+        self.layer_nums = [int(v) for v in s["meta/layer_nums"]]
+        self.strides = [int(v) for v in s["meta/layer_strides"]]
+        self.ups = [int(v) for v in s["meta/upsample_strides"]]
+        self.has_codebook = bool(s["meta/has_codebook"])
+        self.emit_single = bool(s["meta/supervise_single"]) if emit_single_preds is None else bool(emit_single_preds)
+        # ---- a6 / a7: codebook -----------------------------------------------------------------------------
+        self._lut_host = (None, None)
+        if self.has_codebook:
+            c = codebook_constants(self.lib, s, dev, self._refuse_codebook)
+            self.enc_levels, self.segs, self.levels, self.ke, self.kc = c.enc_levels, c.segs, c.levels, c.ke, c.kc
+            self.lut, self.lut_bias, self.level_blobs, self.level_ptrs = c.lut, c.lut_bias, c.level_blobs, c.level_ptrs
+            self._lut_host = (c.lut_host, c.lut_bias_host)             # (for the head tables of ``_set_heads``)
+
+    @staticmethod
+    def _refuse_codebook(ke, kc, D, segs):
+        if ke > 512 or kc > 256:
+            raise NotImplementedError(f"deployed codebook path: seg_num * dict_size <= 512, dict_size <= 256 (got {segs} x {kc}): "
+                                      "the encode kernels' tile budget (qv2x_codebook_encode_f32)")
+        if D != 256:
+            raise NotImplementedError(f"deployed codebook path: a codebook as wide as the 256-channel shared feature (got {D})")
+
+    def _set_heads(self, heads: _Heads, heads_single: Optional[_Heads], tables: bool):
+        """``heads`` / ``heads_single`` and how they run.  ``tables``: heads by table look-up where a table fits (the W8A8 engine).  The
+        fp32 engine passes False: no head tables, ``table_heads`` None and ``single_by_tables`` / ``single_by_global_tables`` False -- its
+        ``*_single`` heads keep the GEMM forms (qv2x_heads_pair_f32 / qv2x_decode_heads_f32) and single-agent scenes the general path."""
+        self.heads, self.heads_single = heads, heads_single
+        self.table_heads, self.single_by_tables, self.single_by_global_tables = None, False, False
+        if not (tables and self.has_codebook):
+            return
+        (lut, lut_bias), dev = self._lut_host, self.dev
+        # the *_single heads see one agent's own decoded feature: with the codebook that is three table rows per cell -- no GEMM
+        self.single_by_tables = (self.heads_single is not None and self.levels <= 4
+                                 and self.levels * self.kc * self.heads_single.cout * 4 <= 60 * 1024)
+        # (round 5: tables past that kernel's LDS -- six planes x 256 rows -- through qv2x_table_heads_f32's global-memory form)
+        # (the C entry's global-memory form: c0 + c1 a multiple of 4 and <= 128, 16-byte aligned arrays -- torch allocations are 256-byte
+        #  aligned; a wider single head keeps qv2x_decode_heads_f32, which handles it: ADVICE r5)
+        self.single_by_global_tables = (not self.single_by_tables and self.heads_single is not None and self.levels <= 16
+                                        and self.heads_single.cout % 4 == 0 and self.heads_single.cout <= 128)
+        if self.single_by_tables or self.single_by_global_tables:
+            self.heads_single.collapse_over_decode(lut, lut_bias, dev)
+        # single-agent scenes (round 4): AttFusion over one agent is the identity, so EVERY head is a table look-up on the agent's own codes
+        # (qv2x_table_heads_f32): cls | reg | dir [+ the *_single heads] stacked, tables = decode table x head weights in float64
+        # (AttFusion or MaxFusion: either is the identity on one agent)
+        sets = [self.heads] + ([self.heads_single] if self.heads_single is not None else [])
+        ct = sum(h.cout for h in sets)
+        ct4 = (ct + 3) // 4 * 4
+        st = ct4 if (ct4 // 4) % 2 else ct4 + 4
+        in_lds = self.levels <= 4 and (self.levels * self.kc * st + 4 * ct4) * 4 <= 160 * 1024
+        # (round 5: tables past the LDS -- seg_num 2 x dict_size 256: six planes, 565 KB -- stay in global memory, qv2x.h)
+        if in_lds or (self.levels <= 16 and ct % 4 == 0 and ct <= 128):
+            t = np.concatenate([np.einsum("lkd,cd->lkc", lut.astype(np.float64), h._w_np) for h in sets], axis=2)
+            b = np.concatenate([lut_bias.astype(np.float64) @ h._w_np.T + h._b_np for h in sets])
+            cat = lambda name: torch.cat([getattr(h, name)[:h.cout] for h in sets]).contiguous()
+            self.table_heads = (_dev(t.astype(np.float32), dev), _dev(b.astype(np.float32), dev), cat("da"), cat("za"),
+                                self.heads.cout, self.heads_single.cout if self.heads_single is not None else 0)
+
+    def _run_heads(self, hd: _Heads, rows, nb, hw):
+        out = torch.empty((nb, hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
+        L.check(self.lib.qv2x_heads_f32(L.ptr(rows), nb * hw, hw, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias),
+                                        L.ptr(hd.da), L.ptr(hd.za), L.ptr(out), L.current_stream()), "qv2x_heads_f32")
+        return out
+
+    # ---- stage interface of the multi-GPU driver (quantv2x_amd/dist.py) -----------------------------------------------------
+    def wire_shape(self):
+        """(levels, H*W) of one agent-frame's code planes -- the payload of the V2X link."""
+        self._workspace(1)
+        return self.levels, self.fh * self.fw
+
+    pairwise_from_poses = _pairwise_from_poses
+
+    def pairwise_frames_from_poses(self, gathered: torch.Tensor, world: int, agent_stride: int, pose_offset: int, frames: int, frame_stride: int,
+                                   max_cav: int, out: torch.Tensor):
+        """the same for ``frames`` scenes in one launch; ``out`` f64 [frames, max_cav, max_cav, 4, 4]"""
+        L.check(self.lib.qv2x_pairwise_from_poses_batch_f64(L.ptr(gathered), world, agent_stride, pose_offset, frames, frame_stride, max_cav,
+                                                            L.ptr(out), L.current_stream()), "qv2x_pairwise_from_poses_batch_f64")
+
+    def fuse_frames_and_heads(self, gathered: torch.Tensor, agent_stride: int, level_stride: int, frame_stride: int, pairwise: torch.Tensor,
+                              n_agents: int, ego: int, own_codes: Optional[torch.Tensor], frames: int) -> dict:
+        """a7-a11 for ``frames`` scenes whose agents' code planes lie ``agent_stride`` bytes apart in ``gathered`` (frame f at
+        ``+ f * frame_stride``); ``pairwise`` f64 [frames, L, L, 4, 4].  With ``own_codes`` (u8 [levels, frames, H*W]) the
+        ``*_single`` heads of this rank's own agent run in the same launch as the heads on the fused maps."""
+        # a world of one agent: the own code planes ARE the scene (pairwise here comes from qv2x_pairwise_from_poses_*: T[0][0] of a world of
+        # one is the identity by construction, so the table look-up's contract holds without a read-back)
+        lens = [n_agents] * frames
+        form = self._post_form(lens, None, own_codes is not None and frame_stride == self.fh * self.fw)
+        return self._post(form, L.ptr(gathered), agent_stride, level_stride, None, pairwise, [f * frame_stride for f in range(frames)], lens, ego,
+                          own_codes, frames)
+
+    # ---- the ego's post stage in row bands (dist.py: shard_post) -----------------------------------------------------------------
+    def band_shape(self):
+        """(cout, H, W) of the stacked cls | reg | dir predictions a band is cut from"""
+        self._workspace(1)
+        return self.heads.cout, self.fh, self.fw
+
+    def head_wire_supported(self, wire: str) -> bool:
+        """Can a band's predictions travel as ``wire``?  "f32" always; "u8" (the output quantizer's codes) iff every channel of the heads
+        has an output quantizer."""
+        if wire not in L.WIRES:
+            raise ValueError(f"wire: one of {sorted(L.WIRES)}, got {wire!r}")
+        return wire == "f32" or bool((self.heads.da_np > 0).all())
+
+    def fuse_frames_and_heads_band(self, gathered: torch.Tensor, agent_stride: int, level_stride: int, frame_stride: int, pairwise: torch.Tensor,
+                                   n_agents: int, ego: int, frames: int, y0: int, y1: int, out_slab: torch.Tensor, wire: str = "f32"):
+        """a7-a11 of ``fuse_frames_and_heads`` for the rows ``[y0, y1)`` of the ego's map only, straight into ``out_slab`` (u8 bytes): the
+        compact band ``[frames][cout][(y1 - y0) * W]`` as fp32 values (``wire="f32"``) or output-quantizer codes (``"u8"``).  Bit for bit the
+        same cells as the whole-map call.  Never the single-agent table look-up (another fp32 association) and no ``*_single`` heads (they are
+        not a function of the ego's map: ``single_preds``).  One launch per 64 frames up to ``_one_launch_agents()`` agents, else the fused
+        rows of the band (a buffer kept per shape: nothing is allocated once warm) and the heads on them -- the whole-map selector's rule."""
+        if not self.head_wire_supported(wire):
+            raise L.Qv2xError("band wire 'u8': a head without an output quantizer has no codes to send")
+        hd, n_cells, esz = self.heads, (y1 - y0) * self.fw, (1 if wire == "u8" else 4)
+        if not 0 <= y0 <= y1 <= self.fh:
+            raise ValueError(f"band rows [{y0}, {y1}) outside the map's {self.fh} rows")
+        if out_slab.dtype != torch.uint8 or out_slab.numel() < frames * hd.cout * n_cells * esz:
+            raise ValueError("out_slab: u8, at least frames * cout * band cells * element size bytes")
+        if n_cells == 0:
+            return
+        one_launch = self.band_one_launch
+        if one_launch is None:
+            one_launch = frames * n_cells // 32 >= self.fuse_heads_min_tiles and n_agents <= self._one_launch_agents()
+        rows = None
+        if not one_launch:
+            key = (frames, n_cells)
+            if self._band_rows is None or self._band_rows[0] != key:
+                self._band_rows = (key, torch.empty((frames, n_cells, 256), dtype=torch.float32, device=self.dev))
+            rows = self._band_rows[1]
+        base, st = out_slab.data_ptr(), L.current_stream()
+        for s0, n, d, offs, cnts, lut, lb in self._scene_chunks(agent_stride, level_stride, pairwise, [f * frame_stride for f in range(frames)],
+                                                                [n_agents] * frames, ego):
+            out = C.c_void_p(base + s0 * hd.cout * n_cells * esz)
+            if one_launch:
+                L.check(self.lib.qv2x_fuse_heads_band(C.byref(d), n, offs, cnts, L.ptr(gathered), lut, lb, None, L.ptr(pairwise[s0]),
+                                                      y0 * self.fw, n_cells, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias), L.ptr(hd.da),
+                                                      L.ptr(hd.za), L.WIRES[wire], L.ptr(hd.da_np), out, None, st), "qv2x_fuse_heads_band")
+            else:
+                L.check(self.lib.qv2x_fuse_att_band_f32(C.byref(d), n, offs, cnts, L.ptr(gathered), lut, lb, None, L.ptr(pairwise[s0]),
+                                                        y0 * self.fw, n_cells, L.ptr(rows[s0]), st), "qv2x_fuse_att_band_f32")
+                L.check(self.lib.qv2x_heads_band(L.ptr(rows[s0]), n, n_cells, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias),
+                                                 L.ptr(hd.da), L.ptr(hd.za), L.WIRES[wire], L.ptr(hd.da_np), out, st), "qv2x_heads_band")
+
+    def assemble_bands(self, gathered_slabs: torch.Tensor, world: int, frames: int, wire: str, out: torch.Tensor):
+        """The gathered band slabs u8 ``[world, slab_bytes]`` -> ``out`` f32 ``[frames, cout, H, W]`` in one launch (qv2x_assemble_bands)."""
+        hd = self.heads
+        L.check(self.lib.qv2x_assemble_bands(L.ptr(gathered_slabs), world, gathered_slabs.shape[1], frames, hd.cout, self.fh, self.fw, L.WIRES[wire],
+                                             L.ptr(hd.da), L.ptr(hd.za), L.ptr(out), L.current_stream()), "qv2x_assemble_bands")
+
+    def band_output(self, preds: torch.Tensor, own_codes: Optional[torch.Tensor], frames: int) -> dict:
+        """The model's output dict from the assembled predictions ``[frames, cout, H, W]``, plus the ``*_single`` heads of this rank's own
+        agent on ``own_codes`` (u8 [levels, frames, H*W]) -- the keys of ``fuse_frames_and_heads``."""
+        out = split_heads(preds, self.heads.splits)
+        if own_codes is not None:
+            out.update(self.single_preds(own_codes, frames))
+        return out
+
+    def decode_rows(self, codes, n_rows_total):
+        """codes u8 [levels, R] -> fp32 [R, 256] (only needed for the *_single heads)."""
+        out = torch.empty((n_rows_total, 256), dtype=torch.float32, device=self.dev)
+        L.check(self.lib.qv2x_decode_lut_f32(L.ptr(codes), n_rows_total, self.levels, self.kc, L.ptr(self.lut),
+                                             L.ptr(self.lut_bias), L.ptr(out), L.current_stream()), "qv2x_decode_lut_f32")
+        return out
+
+    def _fuse_desc(self, agent_stride, level_stride, pairwise_b, n, ego):
+        d = L.FuseDesc()
+        d.agents, d.h, d.w = n, self.fh, self.fw
+        d.levels, d.kc = (self.levels, self.kc) if self.has_codebook else (1, 1)
+        d.max_cav, d.ego = pairwise_b.shape[0], ego
+        d.code_agent_stride, d.code_level_stride = agent_stride, level_stride
+        d.h_metres, d.w_metres, d.discrete_ratio = self.hm, self.wm, self.ratio
+        d.fusion = self.fusion
+        return d
+
+    def fuse(self, codes_ptr, agent_stride, level_stride, feats, pairwise_b, n, out, ego=0):
+        """a7-a10 alone: the fused fp32 map [H*W, 256] into ``out`` (parity tests, benchmarks)."""
+        d = self._fuse_desc(agent_stride, level_stride, pairwise_b, n, ego)
+        lut, lb = self._lut_ptrs()
+        L.check(self.lib.qv2x_fuse_att_f32(C.byref(d), codes_ptr, lut, lb, L.ptr(feats) if feats is not None else None,
+                                           L.ptr(pairwise_b), L.ptr(out), L.current_stream()), "qv2x_fuse_att_f32")
+
+    def _lut_ptrs(self):
+        return (L.ptr(self.lut), L.ptr(self.lut_bias)) if self.has_codebook else (None, None)
+
+    def _scene_chunks(self, agent_stride, level_stride, pairwise, offsets, counts, ego):
+        """The scenes of a batched a7-a10 launch in chunks of 64 (the kernels' scene tables): per chunk ``(first scene, scenes, FuseDesc,
+        offsets i64[], agent counts i32[], decode table, its bias)``."""
+        lut, lb = self._lut_ptrs()
+        for s0 in range(0, len(counts), 64):
+            s1 = min(len(counts), s0 + 64)
+            d = self._fuse_desc(agent_stride, level_stride, pairwise[s0], max(counts[s0:s1]), ego)
+            yield s0, s1 - s0, d, (C.c_int64 * (s1 - s0))(*offsets[s0:s1]), (C.c_int32 * (s1 - s0))(*counts[s0:s1]), lut, lb
+
+    def fuse_scenes(self, codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, counts, out, ego=0):
+        """a7-a10 for several scenes in ONE launch: scene s = ``counts[s]`` agents starting ``offsets[s]`` bytes into the codes (floats into
+        ``feats``); ``pairwise`` f64 [scenes, L, L, 4, 4], ``out`` f32 [scenes, H*W, 256].  Chunks of 64 scenes."""
+        for s0, n, d, offs, cnts, lut, lb in self._scene_chunks(agent_stride, level_stride, pairwise, offsets, counts, ego):
+            L.check(self.lib.qv2x_fuse_att_batch_f32(C.byref(d), n, offs, cnts, codes_ptr, lut, lb,
+                                                     L.ptr(feats) if feats is not None else None, L.ptr(pairwise[s0]), L.ptr(out[s0]),
+                                                     L.current_stream()), "qv2x_fuse_att_batch_f32")
+
+    def _self_transforms_are_identity(self, pairwise: torch.Tensor) -> bool:
+        """The table look-up for single-agent scenes skips the warp: it is only the model's result when ``pairwise[b, 0, 0] = I`` (what
+        ``get_pairwise_transformation`` produces, transformation_utils.py:21-66).  The reference warps with whatever it is handed
+        (AttFusion -> warp_affine_simple, fusion_in_one.py:142-143), so a non-identity self-transform (pose-noise experiments, a caller's
+        bug) must take the general path.  Checked on the host whenever the matrix can be read: a CPU tensor always; a device tensor unless
+        the stream is capturing (the verdict is remembered per tensor OBJECT and version, so a replayed input costs one read-back).  During capture of a
+        device tensor the contract cannot be verified and is assumed -- ``capture()`` runs an eager forward first, which does check."""
+        if pairwise.is_cuda:
+            if torch.cuda.is_current_stream_capturing():
+                return True
+            # The verdict is remembered for the tensor OBJECT (a weak reference) at its version -- never for an address: a fresh tensor that
+            # reuses a freed block has the same data_ptr and version 0 but other contents (ADVICE r5; GPU suite of round 6 hit exactly that).
+            ref = getattr(self, "_ident_ref", None)
+            if ref is not None and ref[0]() is pairwise and ref[1] == pairwise._version:
+                return ref[2]
+            t00 = pairwise[:, 0, 0].cpu()
+        else:
+            t00 = pairwise[:, 0, 0]
+        ok = bool((t00 == torch.eye(4, dtype=t00.dtype)).all())
+        if pairwise.is_cuda:
+            import weakref
+            self._ident_ref = (weakref.ref(pairwise), pairwise._version, ok)
+        return ok
+
+    def _one_launch_agents(self) -> int:
+        """most agents per scene for which a7-a11 run as one launch (see ``fuse_heads_max_agents``)"""
+        batched = self.has_codebook and self.levels == 3
+        return self.fuse_heads_max_agents if batched else min(self.fuse_heads_max_agents, 1)
+
+    def _table_heads_out(self, codes, n: int) -> dict:
+        """The model's output dict for ``n`` single-agent scenes from their code planes u8 [levels, n * H*W] (qv2x_table_heads_f32).
+        Relies on the contract ``pairwise_t_matrix[b, 0, 0] = I`` (``T[i, j] = T_j^-1 T_i``, transformation_utils.py:21-66)."""
+        tab, tb, da, za, c0, c1 = self.table_heads
+        hw = self.fh * self.fw
+        preds = torch.empty((n, c0, self.fh, self.fw), dtype=torch.float32, device=self.dev)
+        sp = torch.empty((n, c1, self.fh, self.fw), dtype=torch.float32, device=self.dev) if c1 else None
+        L.check(self.lib.qv2x_table_heads_f32(L.ptr(codes), n * hw, hw, self.levels, self.kc, c0, c1, L.ptr(tab), L.ptr(tb), L.ptr(da), L.ptr(za),
+                                              L.ptr(preds), L.ptr(sp) if sp is not None else None, L.current_stream()), "qv2x_table_heads_f32")
+        out = split_heads(preds, self.heads.splits)
+        if sp is not None:
+            out.update(split_heads(sp, self.heads_single.splits, "_single"))
+        return out
+
+    def fuse_heads_scenes(self, codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, counts, ego=0, fused_tap=None):
+        """a7-a11 for several scenes in ONE launch per 64 scenes (qv2x_fuse_heads_batch_f32): predictions f32 [scenes, cout, H, W]; the
+        fused map only exists tile by tile in LDS (``fused_tap`` f32 [scenes, H*W, 256], optional, receives a copy)."""
+        hd, hw = self.heads, self.fh * self.fw
+        out = torch.empty((len(counts), hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
+        for s0, n, d, offs, cnts, lut, lb in self._scene_chunks(agent_stride, level_stride, pairwise, offsets, counts, ego):
+            L.check(self.lib.qv2x_fuse_heads_batch_f32(C.byref(d), n, offs, cnts, codes_ptr, lut, lb,
+                                                       L.ptr(feats) if feats is not None else None, L.ptr(pairwise[s0]),
+                                                       hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias), L.ptr(hd.da), L.ptr(hd.za), L.ptr(out[s0]),
+                                                       L.ptr(fused_tap[s0]) if fused_tap is not None else None, L.current_stream()),
+                    "qv2x_fuse_heads_batch_f32")
+        return out
+
+    def _post_form(self, lens: List[int], taps: Optional[dict], identity) -> str:
+        """How a7-a11 run on scenes of ``lens`` agents: "tables" -- every scene one agent, all heads by table look-up on its code planes, only
+        where the contract ``pairwise[b, 0, 0] = I`` holds (``identity``: a bool, or a callable asked last that may read the matrix back);
+        "one_launch" -- qv2x_fuse_heads_batch_f32, no fused map in HBM; or "fused" -- the fused map, then the heads (what ``taps`` need)."""
+        if (taps is None and self.table_heads is not None and self.single_agent_tables and all(n == 1 for n in lens)
+                and (identity() if callable(identity) else identity)):
+            return "tables"
+        if taps is None and len(lens) * self.fh * self.fw // 32 >= self.fuse_heads_min_tiles and max(lens) <= self._one_launch_agents():
+            return "one_launch"
+        return "fused"
+
+    def _post(self, form: str, codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, lens: List[int], ego: int,
+              own: Optional[torch.Tensor], n_own: int, taps: Optional[dict] = None) -> dict:
+        """a7-a11 in ``form`` (``_post_form``) on the scenes ``lens`` -- the agents' code planes at ``codes_ptr`` (``offsets`` in bytes) or
+        their fp32 shared features ``feats`` (``offsets`` in floats), ``pairwise`` f64 [scenes, L, L, 4, 4] -- and the ``*_single`` heads on
+        ``own``, the code planes u8 [levels, n_own * H*W] of the agents that want them (the scenes themselves in the table form; without a
+        codebook the ``*_single`` heads run on ``feats``).  Returns the model's output dict."""
+        if form == "tables":
+            return self._table_heads_out(own, len(lens))
+        hw, nb = self.fh * self.fw, len(lens)
+        single = self.heads_single is not None and own is not None
+        sp = None
+        if form == "one_launch":                                         # decode + warp + fusion + heads, tile by tile: no fused map in HBM
+            preds = self.fuse_heads_scenes(codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, lens, ego)
+            if single:
+                sp = self._decode_heads_single(own, n_own)
+        else:                                                            # every scene of the call in one launch, then the heads
+            fused = torch.empty((nb, hw, 256), dtype=torch.float32, device=self.dev)
+            self.fuse_scenes(codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, lens, fused, ego)
+            if single:                                                   # the heads on the fused map + the *_single heads on the own codes
+                preds, sp = self._heads_pair(fused, nb, own, n_own)
+            else:
+                preds = self._run_heads(self.heads, fused, nb, hw)
+            if taps is not None:
+                taps["fused"] = fused
+        if self.heads_single is not None and sp is None and feats is not None:
+            sp = self._run_heads(self.heads_single, feats, sum(lens), hw)
+        out = split_heads(preds, self.heads.splits)
+        if sp is not None:
+            out.update(split_heads(sp, self.heads_single.splits, "_single"))
+        return out
+
+    def fuse_and_heads(self, codes, agent_stride, level_stride, pairwise_b, n_agents, ego=0) -> dict:
+        """a7-a11 on an (all-gathered) code tensor for one scene; ``pairwise_b`` f64 [L, L, 4, 4] on the device."""
+        return self.fuse_heads_and_single(codes, agent_stride, level_stride, pairwise_b, n_agents, ego, None, 0)
+
+    def _decode_heads_single(self, codes, n_agents: int):
+        hw = self.fh * self.fw
+        hd = self.heads_single
+        sp = torch.empty((n_agents, hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
+        if self.single_by_tables:
+            tab, tb = hd.lut_tables
+            L.check(self.lib.qv2x_single_heads_lut_f32(L.ptr(codes), n_agents * hw, hw, self.levels, self.kc, hd.cout, L.ptr(tab), L.ptr(tb),
+                                                       L.ptr(hd.da), L.ptr(hd.za), L.ptr(sp), L.current_stream()), "qv2x_single_heads_lut_f32")
+            return sp
+        if self.single_by_global_tables:
+            tab, tb = hd.lut_tables
+            L.check(self.lib.qv2x_table_heads_f32(L.ptr(codes), n_agents * hw, hw, self.levels, self.kc, hd.cout, 0, L.ptr(tab), L.ptr(tb),
+                                                  L.ptr(hd.da), L.ptr(hd.za), L.ptr(sp), None, L.current_stream()), "qv2x_table_heads_f32")
+            return sp
+        L.check(self.lib.qv2x_decode_heads_f32(L.ptr(codes), n_agents * hw, hw, self.levels, self.kc, L.ptr(self.lut), L.ptr(self.lut_bias),
+                                               hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias), L.ptr(hd.da), L.ptr(hd.za),
+                                               L.ptr(sp), L.current_stream()), "qv2x_decode_heads_f32")
+        return sp
+
+    def _heads_pair(self, fused, nb, codes, n_agents):
+        """heads on the fused rows [nb*hw, 256] + *_single heads on the agents' own codes [levels, n_agents*hw]"""
+        hw = self.fh * self.fw
+        hd, hs = self.heads, self.heads_single
+        if self.single_by_tables or self.single_by_global_tables:        # the single heads are a table look-up: their own launch
+            return self._run_heads(hd, fused, nb, hw), self._decode_heads_single(codes, n_agents)
+        preds = torch.empty((nb, hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
+        sp = torch.empty((n_agents, hs.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
+        L.check(self.lib.qv2x_heads_pair_f32(L.ptr(fused), nb * hw, hw, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias), L.ptr(hd.da),
+                                             L.ptr(hd.za), L.ptr(preds), L.ptr(codes), n_agents * hw, self.levels, self.kc,
+                                             L.ptr(self.lut), L.ptr(self.lut_bias), hs.cout, hs.cout_pad, L.ptr(hs.w), L.ptr(hs.bias),
+                                             L.ptr(hs.da), L.ptr(hs.za), L.ptr(sp), L.current_stream()), "qv2x_heads_pair_f32")
+        return preds, sp
+
+    def fuse_heads_and_single(self, codes, agent_stride, level_stride, pairwise_b, n_agents, ego, own_codes, n_own: int = 1) -> dict:
+        """``fuse_and_heads`` on the gathered codes plus ``single_preds`` on this rank's own codes, the two head passes in one
+        launch (what one rank of the multi-GPU driver does after the all-gather)."""
+        pairwise = pairwise_b.to(torch.float64).contiguous()[None]      # (one scene of the batched fuse: the same device code, qv2x.h)
+        return self._post("fused", L.ptr(codes), agent_stride, level_stride, None, pairwise, [0], [n_agents], ego, own_codes, n_own)
+
+    def single_preds(self, codes, n_agents: int) -> dict:
+        """``*_preds_single`` (heter_model_baseline.py:224-230): the per-agent heads on each agent's own decoded feature."""
+        if self.heads_single is None:
+            return {}
+        return split_heads(self._decode_heads_single(codes, n_agents), self.heads_single.splits, "_single")
+
+    # ---- the reference's model contract ----------------------------------------------------------------------
+    @torch.no_grad()
+    def forward(self, data_dict: dict, taps: Optional[dict] = None) -> dict:
+        agents = data_dict["agent_modality_list"]
+        n_total = len(agents)
+        if any(a != "m1" for a in agents):
+            raise NotImplementedError("deployed path: every agent is the LiDAR modality 'm1' (a heterogeneous model deploys as DeployedHeterModel)")
+        enc = self.encode_agents(data_dict["inputs_m1"], n_total, taps)
+        return self.finish(enc, n_total, data_dict, taps)
+
+    @torch.no_grad()
+    def finish(self, enc, n_total: int, data_dict: dict, taps: Optional[dict] = None) -> dict:
+        """a7-a11 on the agents' wire data ``enc`` (code planes u8 [levels, n_total * H*W] in agent order, or the i8 shrinker output of a
+        model without a codebook): decode + warp + fusion per scene, the heads, the ``*_single`` heads."""
+        pairwise, lens = scene_layout(data_dict, n_total)
+        hw = self.fh * self.fw
+        # (no workspace of n_total agents here: a codebook model's post stage only needs the code planes it is handed -- the ego engine of a
+        #  heterogeneous scene never encodes n_total agents itself)
+        feats = None if self.has_codebook else self._shared_features(enc, n_total)
+        form = self._post_form(lens, taps, lambda: self._self_transforms_are_identity(data_dict["pairwise_t_matrix"]))   # (the caller's own tensor object: see there)
+        if form != "tables" and not pairwise.is_cuda:                   # a host tensor (the reference's collate output before to_device): copied here
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError("pairwise_t_matrix on the host cannot be uploaded during HIP-graph capture: pass a device tensor")
+            pairwise = pairwise.to(self.dev)
+        starts = [sum(lens[:bi]) for bi in range(len(lens))]
+        if self.has_codebook:
+            out = self._post(form, L.ptr(enc), hw, n_total * hw, None, pairwise, [st * hw for st in starts], lens, 0, enc, n_total, taps)
+        else:
+            out = self._post(form, None, 0, 0, feats, pairwise, [st * hw * 256 for st in starts], lens, 0, None, n_total, taps)
+        if taps is not None:
+            taps["codes"] = enc if self.has_codebook else None
+            taps["features"] = feats
+        return out
+
+    # ---- HIP-graph replay of a fixed-shape frame ---------------------------------------------------------------
+    def capture(self, data_dict: dict):
+        """Capture one frame into a HIP graph (``capture_forward``): the returned callable replays it on the same input tensors.
+
+        The graph relies on the resident canvas being clean between calls (``DeployedModel.pillars_to_canvas``): every path of that class leaves it
+        so; ``pillars_to_canvas(resident=False)`` refuses to run on a workspace that has such graphs.
+        The pillar count M = ``voxel_features.shape[0]`` is baked into the graph: keep M fixed across replays and pad
+        unused rows with an out-of-range agent index (``voxel_coords[:, 0] = -1``), which ``pfn_scatter_kernel`` drops.
+        ``record_len`` (several scenes per call) must be a CPU tensor: its values shape the launch list."""
+        return capture_forward(self, data_dict)
+
+
+class DeployedModel(DeployedPostStage):
+    """The hot path as HIP kernels.  Same call contract as the reference's model: the W8A8 agent stage a1-a6 (PFN or
+    SECOND, backbone plan, shrinker, compressor, the three encode modes, the resident canvas) in front of ``DeployedPostStage``."""
 
     def __init__(self, state: Dict[str, np.ndarray], device="cuda", emit_single_preds: Optional[bool] = None):
-        super().__init__()
-        lut, lut_bias = self._setup_common(state, device, emit_single_preds)
+        super().__init__(state, device, emit_single_preds)
         s, dev = state, self.dev
 
         # ---- a1: PFN parameters (host struct, passed by value to the kernel) -- or a13, the SECOND encoder ------------
@@ -378,20 +908,7 @@ class DeployedModel(nn.Module):
             self.second: Dict[int, object] = {}                        # per agent count: a DeployedSecondEncoder (it owns the canvas)
             self.second_max_voxels, self.second_max_points = 70000, 5
         else:
-            n = "encoder_m1.pillar_vfe.pfn_layers.0.linear"
-            wq = ((s[n + "/w_code"].astype(np.float32) - s[n + "/w_zp"].astype(np.float32)[:, None])
-                  * s[n + "/w_delta"].astype(np.float32)[:, None]).astype(np.float32)
-            if wq.shape != (64, 10):
-                raise NotImplementedError("deployed PFN expects Linear(10 -> 64)")
-            p = L.PfnParams()
-            p.w[:] = wq.reshape(-1).tolist()
-            p.b[:] = s[n + "/bias"].astype(np.float32).tolist()
-            p.d1, p.z1 = float(np.float32(s[n + "/a_delta"])), float(s[n + "/a_zp"])
-            p.d2, p.z2 = float(np.float32(s["pfn/a2_delta"])), float(s["pfn/a2_zp"])
-            p.vox[:] = [float(np.float32(v)) for v in s["meta/voxel"]]
-            p.off[:] = [float(np.float32(v)) for v in s["meta/offset"]]
-            self.pfn = p
-            q = (p.d2, int(p.z2))                                    # quantizer of the canvas
+            self.pfn, q = pfn_params(s)
             self.canvas_c, self.canvas_q = 64, q
 
         # ---- a3: backbone ----------------------------------------------------------------------------------
@@ -434,108 +951,18 @@ class DeployedModel(nn.Module):
             self.comp_channels = narrow                                # what would travel: narrow x H x W bytes per agent
             self.final = self.comp[-1]
         # ---- a11: heads ------------------------------------------------------------------------------------
-        self.heads = _Heads(s, "", dev)
-        self.heads_single = _Heads(s, "_single", dev) if (self.emit_single and "cls_head_single/w_code" in s) else None
-        # the *_single heads see one agent's own decoded feature: with the codebook that is three table rows per cell -- no GEMM
-        self.single_by_tables = (self.heads_single is not None and self.has_codebook and self.levels <= 4
-                                 and self.levels * self.kc * self.heads_single.cout * 4 <= 60 * 1024)
-        # (round 5: tables past that kernel's LDS -- six planes x 256 rows -- through qv2x_table_heads_f32's global-memory form)
-        # (the C entry's global-memory form: c0 + c1 a multiple of 4 and <= 128, 16-byte aligned arrays -- torch allocations are 256-byte
-        #  aligned; a wider single head keeps qv2x_decode_heads_f32, which handles it: ADVICE r5)
-        self.single_by_global_tables = (not self.single_by_tables and self.heads_single is not None and self.has_codebook and self.levels <= 16
-                                        and self.heads_single.cout % 4 == 0 and self.heads_single.cout <= 128)
-        if self.single_by_tables or self.single_by_global_tables:
-            self.heads_single.collapse_over_decode(lut, lut_bias, dev)
-        # single-agent scenes (round 4): AttFusion over one agent is the identity, so EVERY head is a table look-up on the agent's own codes
-        # (qv2x_table_heads_f32): cls | reg | dir [+ the *_single heads] stacked, tables = decode table x head weights in float64
-        self.table_heads = None
-        if self.has_codebook:                                            # (AttFusion or MaxFusion: either is the identity on one agent)
-            sets = [self.heads] + ([self.heads_single] if self.heads_single is not None else [])
-            ct = sum(h.cout for h in sets)
-            ct4 = (ct + 3) // 4 * 4
-            st = ct4 if (ct4 // 4) % 2 else ct4 + 4
-            in_lds = self.levels <= 4 and (self.levels * self.kc * st + 4 * ct4) * 4 <= 160 * 1024
-            # (round 5: tables past the LDS -- seg_num 2 x dict_size 256: six planes, 565 KB -- stay in global memory, qv2x.h)
-            if in_lds or (self.levels <= 16 and ct % 4 == 0 and ct <= 128):
-                t = np.concatenate([np.einsum("lkd,cd->lkc", lut.astype(np.float64), h._w_np) for h in sets], axis=2)
-                b = np.concatenate([lut_bias.astype(np.float64) @ h._w_np.T + h._b_np for h in sets])
-                cat = lambda name: torch.cat([getattr(h, name)[:h.cout] for h in sets]).contiguous()
-                self.table_heads = (_dev(t.astype(np.float32), dev), _dev(b.astype(np.float32), dev), cat("da"), cat("za"),
-                                    self.heads.cout, self.heads_single.cout if self.heads_single is not None else 0)
+        self._set_heads(_Heads(s, "", dev), _Heads(s, "_single", dev) if (self.emit_single and "cls_head_single/w_code" in s) else None,
+                        tables=True)
         self._bufs: Dict[int, dict] = {}
         # launch-plan switches for the ablation tools (tools/bench_*_abl.py); the defaults are the shipped configuration
         self.use_wide_conv, self.batch_deconvs, self.use_chains = True, True, True
         self.chain_max_agents = 1
-
-    # ------------------------------------------------------------------------------------------------------
-    def _setup_common(self, state: Dict[str, np.ndarray], device, emit_single_preds: Optional[bool]):
-        """What every engine of this network sets up first (the fp32 one too): the library and the device, the state's metadata and --
-        with a codebook -- the decode table and the encode's level blobs.  Returns the decode table on the host, ``(lut [levels][kc][256],
-        lut_bias [256])``, or ``(None, None)``."""
-        self.lib = L.load()                      # raises if libqv2x.so is absent: no fallback
-        if not torch.cuda.is_available():
-            raise L.Qv2xError(f"{type(self).__name__} needs an MI355X (torch.cuda.is_available() is False)")
-        self.state, self.dev = state, torch.device(device)
-        s, dev = state, self.dev
-        if str(s.get("meta/fusion_method", "att")) not in ("att", "max"):
-            raise NotImplementedError(f"deployed path: fusion_method {s['meta/fusion_method']!r} ('att' = AttFusion and 'max' = MaxFusion are built here)")
-        self.fusion = 1 if str(s.get("meta/fusion_method", "att")) == "max" else 0
-        self.nx, self.ny, _ = (int(v) for v in s["meta/grid"])
-        self.hm, self.wm = (float(v) for v in s["meta/HW_metres"])
-        self.ratio = float(s["meta/discrete_ratio"])
-        self.layer_nums = [int(v) for v in s["meta/layer_nums"]]
-        self.strides = [int(v) for v in s["meta/layer_strides"]]
-        self.ups = [int(v) for v in s["meta/upsample_strides"]]
-        self.has_codebook = bool(s["meta/has_codebook"])
-        self.emit_single = bool(s["meta/supervise_single"]) if emit_single_preds is None else bool(emit_single_preds)
-        # ---- a6 / a7: codebook -----------------------------------------------------------------------------
-        lut = lut_bias = None
-        if self.has_codebook:
-            # seg_num (m) > 1: the state holds the EXTENDED codebook [m * kc][D] (ptq_state.extended_codebook).  Downstream of the encode
-            # everything counts code PLANES: ``levels`` = residual levels * m (the wire's [levels][agents][H*W] planes and the decode table
-            # [levels][kc][D], which is the per-level table over the extended rows read plane by plane); the encode kernels get the true
-            # level count ``enc_levels`` and ``segs``.
-            self.enc_levels, self.segs = int(s["meta/codebook_levels"]), int(s.get("meta/codebook_segs", 1))
-            self.levels = self.enc_levels * self.segs
-            self.ke = int(s["codebook/0/codebook"].shape[0])
-            self.kc = self.ke // self.segs
-            if self.ke > 512 or self.kc > 256:
-                raise NotImplementedError(f"deployed codebook path: seg_num * dict_size <= 512, dict_size <= 256 (got {self.segs} x {self.kc}): "
-                                          "the encode kernels' tile budget (qv2x_codebook_encode_f32)")
-            lut, lut_bias = decode_tables(s, self.enc_levels)
-            lut = lut.reshape(self.levels, self.kc, lut.shape[-1])
-            self.lut = _dev(lut, dev)
-            self.lut_bias = _dev(lut_bias, dev)
-            self.level_blobs = [self._level_blob(l) for l in range(self.enc_levels)]
-            self.level_ptrs = (C.c_void_p * self.enc_levels)(*[b.data_ptr() for b in self.level_blobs])
         # "exact": every cell through the reference's eleven chained GEMMs.  "two_stage" (round 6, the default wherever its contract holds):
         # the SAME indices by construction -- exact integer candidates, the chain only for the cells a proven bound cannot decide
         # (encode_two_stage.py; its operands are built with the first workspace).  "collapsed": opt-in and approximate, see collapse_encoder.
         self._collapsed, self._two_stage, self.two_stage_refused = None, None, None
         self.encode_form = "auto"                                      # "wave": force the wave-per-32-cells encode kernel on every cell (same codes)
         self.encode_mode = "two_stage" if self.two_stage_supported() else "exact"
-        return lut, lut_bias
-
-    # ------------------------------------------------------------------------------------------------------
-    def _level_blob(self, l: int) -> torch.Tensor:
-        s, kc = self.state, self.ke                                     # (rows of the extended codebook)
-        g = lambda n: s[f"codebook/{l}/{n}"].astype(np.float32)
-        zeros_w, zeros_b = np.zeros((64, 256, 4), np.float32), np.zeros(256, np.float32)
-        last = f"codebook/{l}/lhead_w" not in s
-        cb = g("codebook")
-        parts = [_pack_k4p(g("stage_w")), g("stage_b"), _pack_k4p(g("qhead_w")), g("qhead_b"),
-                 zeros_w if last else _pack_k4p(g("lhead_w")), zeros_b if last else g("lhead_b"),
-                 _pack_k4p(cb), cb, np.zeros(kc, np.float32)]
-        flat = np.concatenate([p.reshape(-1) for p in parts])
-        wg = flat.size                                                 # the workgroup form's section ends with c2
-        flat = np.concatenate([flat, wave_section(g("stage_w"), g("qhead_w"), np.zeros((256, 256), np.float32) if last else g("lhead_w"), cb, self.segs)])
-        assert flat.size == self.lib.qv2x_codebook_level_floats(kc)
-        blob = _dev(flat, self.dev)
-        cb_off = wg - kc - kc * 256
-        L.check(self.lib.qv2x_codebook_c2_f32(C.c_void_p(blob.data_ptr() + 4 * cb_off), kc,
-                                              C.c_void_p(blob.data_ptr() + 4 * (wg - kc)), L.current_stream()),
-                "qv2x_codebook_c2_f32")
-        return blob
 
     def _padded(self, n, h, w, c, q):
         """Padded i8 BEV tensor with the border (and interior) preset to the code of 0.0."""
@@ -648,12 +1075,6 @@ class DeployedModel(nn.Module):
                                               arr([it[0].bias for it in items]), arr([it[4] for it in items]), L.current_stream()),
                 "qv2x_deconv_i8_batch")
 
-    def _run_heads(self, hd: _Heads, rows, nb, hw):
-        out = torch.empty((nb, hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
-        L.check(self.lib.qv2x_heads_f32(L.ptr(rows), nb * hw, hw, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias),
-                                        L.ptr(hd.da), L.ptr(hd.za), L.ptr(out), L.current_stream()), "qv2x_heads_f32")
-        return out
-
     # ---- stages (also used one by one by the parity tests and the multi-GPU driver) --------------------------
     def conv_plan(self, n_agents: int):
         """Static launch list of a3 + a4 for ``n_agents`` agents: ``(kind, layer, x, h, w, out, out_c0, macs)``."""
@@ -728,13 +1149,9 @@ class DeployedModel(nn.Module):
         ``clear_pillars`` once the first convolution has read it, so the 9 MB-per-frame fill is skipped while the canvas is known clean."""
         b = self._workspace(n_agents)
         st = L.current_stream()
-        vf = inputs["voxel_features"].contiguous()
-        co = inputs["voxel_coords"].to(torch.int32).contiguous()
-        npnt = inputs["voxel_num_points"].to(torch.int32).contiguous()
+        vf, co, npnt = pillar_inputs(inputs, pfn=self.encoder_kind != "second")
         if self.encoder_kind == "second":                             # a13: MeanVFE + sparse convolutions + height compression
             return self.second[n_agents]({"voxel_features": vf, "voxel_coords": co, "voxel_num_points": npnt})
-        if vf.dtype != torch.float32 or vf.dim() != 3 or tuple(vf.shape[1:]) != (32, 4):
-            raise ValueError("voxel_features must be float32 [M, 32, 4]")
         canvas = b["canvas"]
         # INVARIANT of the resident canvas: between calls it holds the code of 0.0 everywhere (`canvas_clean`), so a resident call needs
         # no fill -- and a HIP graph captured in that state contains none.  Such a graph cannot see this host flag: once one exists
@@ -864,12 +1281,6 @@ class DeployedModel(nn.Module):
         cells = n_agents * self.fh * self.fw
         return {"cells": cells, "refined": int(c[0]), "refined_fraction": float(c[0]) / cells, "first_flagged_at_level": [int(v) for v in c[1:1 + self.enc_levels]]}
 
-    # ---- stage interface of the multi-GPU driver (quantv2x_amd/dist.py) -----------------------------------------------------
-    def wire_shape(self):
-        """(levels, H*W) of one agent-frame's code planes -- the payload of the V2X link."""
-        self._workspace(1)
-        return self.levels, self.fh * self.fw
-
     def encode_into(self, inputs: dict, frames: int, codes_out: torch.Tensor):
         """a1-a6 for ``frames`` frames of ONE agent (batch index = frame); codes u8 [levels, frames, H*W] written to ``codes_out``."""
         self.pillars_to_canvas(inputs, frames, resident=True)
@@ -880,100 +1291,6 @@ class DeployedModel(nn.Module):
             self._restore_canvas(frames)
             raise
         return self.encode_codes(frames, out=codes_out)
-
-    def pairwise_from_poses(self, gathered: torch.Tensor, world: int, agent_stride: int, pose_offset: int, max_cav: int, out: torch.Tensor):
-        """pairwise f64 [max_cav, max_cav, 4, 4] from the poses inside the gathered payloads (qv2x_pairwise_from_poses_f64)."""
-        L.check(self.lib.qv2x_pairwise_from_poses_f64(L.ptr(gathered), world, agent_stride, pose_offset, max_cav, L.ptr(out),
-                                                      L.current_stream()), "qv2x_pairwise_from_poses_f64")
-
-    def pairwise_frames_from_poses(self, gathered: torch.Tensor, world: int, agent_stride: int, pose_offset: int, frames: int, frame_stride: int,
-                                   max_cav: int, out: torch.Tensor):
-        """the same for ``frames`` scenes in one launch; ``out`` f64 [frames, max_cav, max_cav, 4, 4]"""
-        L.check(self.lib.qv2x_pairwise_from_poses_batch_f64(L.ptr(gathered), world, agent_stride, pose_offset, frames, frame_stride, max_cav,
-                                                            L.ptr(out), L.current_stream()), "qv2x_pairwise_from_poses_batch_f64")
-
-    def fuse_frames_and_heads(self, gathered: torch.Tensor, agent_stride: int, level_stride: int, frame_stride: int, pairwise: torch.Tensor,
-                              n_agents: int, ego: int, own_codes: Optional[torch.Tensor], frames: int) -> dict:
-        """a7-a11 for ``frames`` scenes whose agents' code planes lie ``agent_stride`` bytes apart in ``gathered`` (frame f at
-        ``+ f * frame_stride``); ``pairwise`` f64 [frames, L, L, 4, 4].  With ``own_codes`` (u8 [levels, frames, H*W]) the
-        ``*_single`` heads of this rank's own agent run in the same launch as the heads on the fused maps."""
-        # a world of one agent: the own code planes ARE the scene (pairwise here comes from qv2x_pairwise_from_poses_*: T[0][0] of a world of
-        # one is the identity by construction, so the table look-up's contract holds without a read-back)
-        lens = [n_agents] * frames
-        form = self._post_form(lens, None, own_codes is not None and frame_stride == self.fh * self.fw)
-        return self._post(form, L.ptr(gathered), agent_stride, level_stride, None, pairwise, [f * frame_stride for f in range(frames)], lens, ego,
-                          own_codes, frames)
-
-    # ---- the ego's post stage in row bands (dist.py: shard_post) -----------------------------------------------------------------
-    def band_shape(self):
-        """(cout, H, W) of the stacked cls | reg | dir predictions a band is cut from"""
-        self._workspace(1)
-        return self.heads.cout, self.fh, self.fw
-
-    def head_wire_supported(self, wire: str) -> bool:
-        """Can a band's predictions travel as ``wire``?  "f32" always; "u8" (the output quantizer's codes) iff every channel of the heads
-        has an output quantizer."""
-        if wire not in L.WIRES:
-            raise ValueError(f"wire: one of {sorted(L.WIRES)}, got {wire!r}")
-        return wire == "f32" or bool((self.heads.da_np > 0).all())
-
-    def fuse_frames_and_heads_band(self, gathered: torch.Tensor, agent_stride: int, level_stride: int, frame_stride: int, pairwise: torch.Tensor,
-                                   n_agents: int, ego: int, frames: int, y0: int, y1: int, out_slab: torch.Tensor, wire: str = "f32"):
-        """a7-a11 of ``fuse_frames_and_heads`` for the rows ``[y0, y1)`` of the ego's map only, straight into ``out_slab`` (u8 bytes): the
-        compact band ``[frames][cout][(y1 - y0) * W]`` as fp32 values (``wire="f32"``) or output-quantizer codes (``"u8"``).  Bit for bit the
-        same cells as the whole-map call.  Never the single-agent table look-up (another fp32 association) and no ``*_single`` heads (they are
-        not a function of the ego's map: ``single_preds``).  One launch per 64 frames up to ``_one_launch_agents()`` agents, else the fused
-        rows of the band (a buffer kept per shape: nothing is allocated once warm) and the heads on them -- the whole-map selector's rule."""
-        if not self.head_wire_supported(wire):
-            raise L.Qv2xError("band wire 'u8': a head without an output quantizer has no codes to send")
-        hd, n_cells, esz = self.heads, (y1 - y0) * self.fw, (1 if wire == "u8" else 4)
-        if not 0 <= y0 <= y1 <= self.fh:
-            raise ValueError(f"band rows [{y0}, {y1}) outside the map's {self.fh} rows")
-        if out_slab.dtype != torch.uint8 or out_slab.numel() < frames * hd.cout * n_cells * esz:
-            raise ValueError("out_slab: u8, at least frames * cout * band cells * element size bytes")
-        if n_cells == 0:
-            return
-        one_launch = self.band_one_launch
-        if one_launch is None:
-            one_launch = frames * n_cells // 32 >= self.fuse_heads_min_tiles and n_agents <= self._one_launch_agents()
-        rows = None
-        if not one_launch:
-            key = (frames, n_cells)
-            if self._band_rows is None or self._band_rows[0] != key:
-                self._band_rows = (key, torch.empty((frames, n_cells, 256), dtype=torch.float32, device=self.dev))
-            rows = self._band_rows[1]
-        lut = L.ptr(self.lut) if self.has_codebook else None
-        lb = L.ptr(self.lut_bias) if self.has_codebook else None
-        base, st = out_slab.data_ptr(), L.current_stream()
-        for s0 in range(0, frames, 64):
-            s1 = min(frames, s0 + 64)
-            d = self._fuse_desc(agent_stride, level_stride, pairwise[s0], n_agents, ego)
-            offs = (C.c_int64 * (s1 - s0))(*[f * frame_stride for f in range(s0, s1)])
-            cnts = (C.c_int32 * (s1 - s0))(*([n_agents] * (s1 - s0)))
-            out = C.c_void_p(base + s0 * hd.cout * n_cells * esz)
-            if one_launch:
-                L.check(self.lib.qv2x_fuse_heads_band(C.byref(d), s1 - s0, offs, cnts, L.ptr(gathered), lut, lb, None, L.ptr(pairwise[s0]),
-                                                      y0 * self.fw, n_cells, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias), L.ptr(hd.da),
-                                                      L.ptr(hd.za), L.WIRES[wire], L.ptr(hd.da_np), out, None, st), "qv2x_fuse_heads_band")
-            else:
-                L.check(self.lib.qv2x_fuse_att_band_f32(C.byref(d), s1 - s0, offs, cnts, L.ptr(gathered), lut, lb, None, L.ptr(pairwise[s0]),
-                                                        y0 * self.fw, n_cells, L.ptr(rows[s0]), st), "qv2x_fuse_att_band_f32")
-                L.check(self.lib.qv2x_heads_band(L.ptr(rows[s0]), s1 - s0, n_cells, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias),
-                                                 L.ptr(hd.da), L.ptr(hd.za), L.WIRES[wire], L.ptr(hd.da_np), out, st), "qv2x_heads_band")
-
-    def assemble_bands(self, gathered_slabs: torch.Tensor, world: int, frames: int, wire: str, out: torch.Tensor):
-        """The gathered band slabs u8 ``[world, slab_bytes]`` -> ``out`` f32 ``[frames, cout, H, W]`` in one launch (qv2x_assemble_bands)."""
-        hd = self.heads
-        L.check(self.lib.qv2x_assemble_bands(L.ptr(gathered_slabs), world, gathered_slabs.shape[1], frames, hd.cout, self.fh, self.fw, L.WIRES[wire],
-                                             L.ptr(hd.da), L.ptr(hd.za), L.ptr(out), L.current_stream()), "qv2x_assemble_bands")
-
-    def band_output(self, preds: torch.Tensor, own_codes: Optional[torch.Tensor], frames: int) -> dict:
-        """The model's output dict from the assembled predictions ``[frames, cout, H, W]``, plus the ``*_single`` heads of this rank's own
-        agent on ``own_codes`` (u8 [levels, frames, H*W]) -- the keys of ``fuse_frames_and_heads``."""
-        out = split_heads(preds, self.heads.splits)
-        if own_codes is not None:
-            out.update(self.single_preds(own_codes, frames))
-        return out
 
     def encode_agents(self, inputs: dict, n_agents: int, taps: Optional[dict] = None):
         """a1-a6 for ``n_agents`` agents.  Returns codes u8 [levels, n, H*W] (or the i8 shrinker output without a codebook)."""
@@ -994,198 +1311,6 @@ class DeployedModel(nn.Module):
                 taps[c.name] = out
         return self.encode_codes(n_agents) if self.has_codebook else (b["comp"][-1] if self.compress else b["s1"])
 
-    def decode_rows(self, codes, n_rows_total):
-        """codes u8 [levels, R] -> fp32 [R, 256] (only needed for the *_single heads)."""
-        out = torch.empty((n_rows_total, 256), dtype=torch.float32, device=self.dev)
-        L.check(self.lib.qv2x_decode_lut_f32(L.ptr(codes), n_rows_total, self.levels, self.kc, L.ptr(self.lut),
-                                             L.ptr(self.lut_bias), L.ptr(out), L.current_stream()), "qv2x_decode_lut_f32")
-        return out
-
-    def _fuse_desc(self, agent_stride, level_stride, pairwise_b, n, ego):
-        d = L.FuseDesc()
-        d.agents, d.h, d.w = n, self.fh, self.fw
-        d.levels, d.kc = (self.levels, self.kc) if self.has_codebook else (1, 1)
-        d.max_cav, d.ego = pairwise_b.shape[0], ego
-        d.code_agent_stride, d.code_level_stride = agent_stride, level_stride
-        d.h_metres, d.w_metres, d.discrete_ratio = self.hm, self.wm, self.ratio
-        d.fusion = self.fusion
-        return d
-
-    def fuse(self, codes_ptr, agent_stride, level_stride, feats, pairwise_b, n, out, ego=0):
-        """a7-a10 alone: the fused fp32 map [H*W, 256] into ``out`` (parity tests, benchmarks)."""
-        d = self._fuse_desc(agent_stride, level_stride, pairwise_b, n, ego)
-        lut = L.ptr(self.lut) if self.has_codebook else None
-        lb = L.ptr(self.lut_bias) if self.has_codebook else None
-        L.check(self.lib.qv2x_fuse_att_f32(C.byref(d), codes_ptr, lut, lb, L.ptr(feats) if feats is not None else None,
-                                           L.ptr(pairwise_b), L.ptr(out), L.current_stream()), "qv2x_fuse_att_f32")
-
-    def fuse_scenes(self, codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, counts, out, ego=0):
-        """a7-a10 for several scenes in ONE launch: scene s = ``counts[s]`` agents starting ``offsets[s]`` bytes into the codes (floats into
-        ``feats``); ``pairwise`` f64 [scenes, L, L, 4, 4], ``out`` f32 [scenes, H*W, 256].  Chunks of 64 scenes."""
-        for s0 in range(0, len(counts), 64):
-            s1 = min(len(counts), s0 + 64)
-            d = self._fuse_desc(agent_stride, level_stride, pairwise[s0], max(counts[s0:s1]), ego)
-            offs = (C.c_int64 * (s1 - s0))(*offsets[s0:s1])
-            cnts = (C.c_int32 * (s1 - s0))(*counts[s0:s1])
-            lut = L.ptr(self.lut) if self.has_codebook else None
-            lb = L.ptr(self.lut_bias) if self.has_codebook else None
-            L.check(self.lib.qv2x_fuse_att_batch_f32(C.byref(d), s1 - s0, offs, cnts, codes_ptr, lut, lb,
-                                                     L.ptr(feats) if feats is not None else None, L.ptr(pairwise[s0]), L.ptr(out[s0]),
-                                                     L.current_stream()), "qv2x_fuse_att_batch_f32")
-
-    def _self_transforms_are_identity(self, pairwise: torch.Tensor) -> bool:
-        """The table look-up for single-agent scenes skips the warp: it is only the model's result when ``pairwise[b, 0, 0] = I`` (what
-        ``get_pairwise_transformation`` produces, transformation_utils.py:21-66).  The reference warps with whatever it is handed
-        (AttFusion -> warp_affine_simple, fusion_in_one.py:142-143), so a non-identity self-transform (pose-noise experiments, a caller's
-        bug) must take the general path.  Checked on the host whenever the matrix can be read: a CPU tensor always; a device tensor unless
-        the stream is capturing (the verdict is remembered per tensor OBJECT and version, so a replayed input costs one read-back).  During capture of a
-        device tensor the contract cannot be verified and is assumed -- ``capture()`` runs an eager forward first, which does check."""
-        if pairwise.is_cuda:
-            if torch.cuda.is_current_stream_capturing():
-                return True
-            # The verdict is remembered for the tensor OBJECT (a weak reference) at its version -- never for an address: a fresh tensor that
-            # reuses a freed block has the same data_ptr and version 0 but other contents (ADVICE r5; GPU suite of round 6 hit exactly that).
-            ref = getattr(self, "_ident_ref", None)
-            if ref is not None and ref[0]() is pairwise and ref[1] == pairwise._version:
-                return ref[2]
-            t00 = pairwise[:, 0, 0].cpu()
-        else:
-            t00 = pairwise[:, 0, 0]
-        ok = bool((t00 == torch.eye(4, dtype=t00.dtype)).all())
-        if pairwise.is_cuda:
-            import weakref
-            self._ident_ref = (weakref.ref(pairwise), pairwise._version, ok)
-        return ok
-
-    def _one_launch_agents(self) -> int:
-        """most agents per scene for which a7-a11 run as one launch (see ``fuse_heads_max_agents``)"""
-        batched = self.has_codebook and self.levels == 3
-        return self.fuse_heads_max_agents if batched else min(self.fuse_heads_max_agents, 1)
-
-    def _table_heads_out(self, codes, n: int) -> dict:
-        """The model's output dict for ``n`` single-agent scenes from their code planes u8 [levels, n * H*W] (qv2x_table_heads_f32).
-        Relies on the contract ``pairwise_t_matrix[b, 0, 0] = I`` (``T[i, j] = T_j^-1 T_i``, transformation_utils.py:21-66)."""
-        tab, tb, da, za, c0, c1 = self.table_heads
-        hw = self.fh * self.fw
-        preds = torch.empty((n, c0, self.fh, self.fw), dtype=torch.float32, device=self.dev)
-        sp = torch.empty((n, c1, self.fh, self.fw), dtype=torch.float32, device=self.dev) if c1 else None
-        L.check(self.lib.qv2x_table_heads_f32(L.ptr(codes), n * hw, hw, self.levels, self.kc, c0, c1, L.ptr(tab), L.ptr(tb), L.ptr(da), L.ptr(za),
-                                              L.ptr(preds), L.ptr(sp) if sp is not None else None, L.current_stream()), "qv2x_table_heads_f32")
-        out = split_heads(preds, self.heads.splits)
-        if sp is not None:
-            out.update(split_heads(sp, self.heads_single.splits, "_single"))
-        return out
-
-    def fuse_heads_scenes(self, codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, counts, ego=0, fused_tap=None):
-        """a7-a11 for several scenes in ONE launch per 64 scenes (qv2x_fuse_heads_batch_f32): predictions f32 [scenes, cout, H, W]; the
-        fused map only exists tile by tile in LDS (``fused_tap`` f32 [scenes, H*W, 256], optional, receives a copy)."""
-        hd, hw = self.heads, self.fh * self.fw
-        out = torch.empty((len(counts), hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
-        for s0 in range(0, len(counts), 64):
-            s1 = min(len(counts), s0 + 64)
-            d = self._fuse_desc(agent_stride, level_stride, pairwise[s0], max(counts[s0:s1]), ego)
-            offs = (C.c_int64 * (s1 - s0))(*offsets[s0:s1])
-            cnts = (C.c_int32 * (s1 - s0))(*counts[s0:s1])
-            lut = L.ptr(self.lut) if self.has_codebook else None
-            lb = L.ptr(self.lut_bias) if self.has_codebook else None
-            L.check(self.lib.qv2x_fuse_heads_batch_f32(C.byref(d), s1 - s0, offs, cnts, codes_ptr, lut, lb,
-                                                       L.ptr(feats) if feats is not None else None, L.ptr(pairwise[s0]),
-                                                       hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias), L.ptr(hd.da), L.ptr(hd.za), L.ptr(out[s0]),
-                                                       L.ptr(fused_tap[s0]) if fused_tap is not None else None, L.current_stream()),
-                    "qv2x_fuse_heads_batch_f32")
-        return out
-
-    def _post_form(self, lens: List[int], taps: Optional[dict], identity) -> str:
-        """How a7-a11 run on scenes of ``lens`` agents: "tables" -- every scene one agent, all heads by table look-up on its code planes, only
-        where the contract ``pairwise[b, 0, 0] = I`` holds (``identity``: a bool, or a callable asked last that may read the matrix back);
-        "one_launch" -- qv2x_fuse_heads_batch_f32, no fused map in HBM; or "fused" -- the fused map, then the heads (what ``taps`` need)."""
-        if (taps is None and self.table_heads is not None and self.single_agent_tables and all(n == 1 for n in lens)
-                and (identity() if callable(identity) else identity)):
-            return "tables"
-        if taps is None and len(lens) * self.fh * self.fw // 32 >= self.fuse_heads_min_tiles and max(lens) <= self._one_launch_agents():
-            return "one_launch"
-        return "fused"
-
-    def _post(self, form: str, codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, lens: List[int], ego: int,
-              own: Optional[torch.Tensor], n_own: int, taps: Optional[dict] = None) -> dict:
-        """a7-a11 in ``form`` (``_post_form``) on the scenes ``lens`` -- the agents' code planes at ``codes_ptr`` (``offsets`` in bytes) or
-        their fp32 shared features ``feats`` (``offsets`` in floats), ``pairwise`` f64 [scenes, L, L, 4, 4] -- and the ``*_single`` heads on
-        ``own``, the code planes u8 [levels, n_own * H*W] of the agents that want them (the scenes themselves in the table form; without a
-        codebook the ``*_single`` heads run on ``feats``).  Returns the model's output dict."""
-        if form == "tables":
-            return self._table_heads_out(own, len(lens))
-        hw, nb = self.fh * self.fw, len(lens)
-        single = self.heads_single is not None and own is not None
-        sp = None
-        if form == "one_launch":                                         # decode + warp + fusion + heads, tile by tile: no fused map in HBM
-            preds = self.fuse_heads_scenes(codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, lens, ego)
-            if single:
-                sp = self._decode_heads_single(own, n_own)
-        else:                                                            # every scene of the call in one launch, then the heads
-            fused = torch.empty((nb, hw, 256), dtype=torch.float32, device=self.dev)
-            self.fuse_scenes(codes_ptr, agent_stride, level_stride, feats, pairwise, offsets, lens, fused, ego)
-            if single:                                                   # the heads on the fused map + the *_single heads on the own codes
-                preds, sp = self._heads_pair(fused, nb, own, n_own)
-            else:
-                preds = self._run_heads(self.heads, fused, nb, hw)
-            if taps is not None:
-                taps["fused"] = fused
-        if self.heads_single is not None and sp is None and feats is not None:
-            sp = self._run_heads(self.heads_single, feats, sum(lens), hw)
-        out = split_heads(preds, self.heads.splits)
-        if sp is not None:
-            out.update(split_heads(sp, self.heads_single.splits, "_single"))
-        return out
-
-    def fuse_and_heads(self, codes, agent_stride, level_stride, pairwise_b, n_agents, ego=0) -> dict:
-        """a7-a11 on an (all-gathered) code tensor for one scene; ``pairwise_b`` f64 [L, L, 4, 4] on the device."""
-        return self.fuse_heads_and_single(codes, agent_stride, level_stride, pairwise_b, n_agents, ego, None, 0)
-
-    def _decode_heads_single(self, codes, n_agents: int):
-        hw = self.fh * self.fw
-        hd = self.heads_single
-        sp = torch.empty((n_agents, hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
-        if self.single_by_tables:
-            tab, tb = hd.lut_tables
-            L.check(self.lib.qv2x_single_heads_lut_f32(L.ptr(codes), n_agents * hw, hw, self.levels, self.kc, hd.cout, L.ptr(tab), L.ptr(tb),
-                                                       L.ptr(hd.da), L.ptr(hd.za), L.ptr(sp), L.current_stream()), "qv2x_single_heads_lut_f32")
-            return sp
-        if self.single_by_global_tables:
-            tab, tb = hd.lut_tables
-            L.check(self.lib.qv2x_table_heads_f32(L.ptr(codes), n_agents * hw, hw, self.levels, self.kc, hd.cout, 0, L.ptr(tab), L.ptr(tb),
-                                                  L.ptr(hd.da), L.ptr(hd.za), L.ptr(sp), None, L.current_stream()), "qv2x_table_heads_f32")
-            return sp
-        L.check(self.lib.qv2x_decode_heads_f32(L.ptr(codes), n_agents * hw, hw, self.levels, self.kc, L.ptr(self.lut), L.ptr(self.lut_bias),
-                                               hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias), L.ptr(hd.da), L.ptr(hd.za),
-                                               L.ptr(sp), L.current_stream()), "qv2x_decode_heads_f32")
-        return sp
-
-    def _heads_pair(self, fused, nb, codes, n_agents):
-        """heads on the fused rows [nb*hw, 256] + *_single heads on the agents' own codes [levels, n_agents*hw]"""
-        hw = self.fh * self.fw
-        hd, hs = self.heads, self.heads_single
-        if self.single_by_tables or self.single_by_global_tables:        # the single heads are a table look-up: their own launch
-            return self._run_heads(hd, fused, nb, hw), self._decode_heads_single(codes, n_agents)
-        preds = torch.empty((nb, hd.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
-        sp = torch.empty((n_agents, hs.cout, self.fh, self.fw), dtype=torch.float32, device=self.dev)
-        L.check(self.lib.qv2x_heads_pair_f32(L.ptr(fused), nb * hw, hw, hd.cout, hd.cout_pad, L.ptr(hd.w), L.ptr(hd.bias), L.ptr(hd.da),
-                                             L.ptr(hd.za), L.ptr(preds), L.ptr(codes), n_agents * hw, self.levels, self.kc,
-                                             L.ptr(self.lut), L.ptr(self.lut_bias), hs.cout, hs.cout_pad, L.ptr(hs.w), L.ptr(hs.bias),
-                                             L.ptr(hs.da), L.ptr(hs.za), L.ptr(sp), L.current_stream()), "qv2x_heads_pair_f32")
-        return preds, sp
-
-    def fuse_heads_and_single(self, codes, agent_stride, level_stride, pairwise_b, n_agents, ego, own_codes, n_own: int = 1) -> dict:
-        """``fuse_and_heads`` on the gathered codes plus ``single_preds`` on this rank's own codes, the two head passes in one
-        launch (what one rank of the multi-GPU driver does after the all-gather)."""
-        pairwise = pairwise_b.to(torch.float64).contiguous()[None]      # (one scene of the batched fuse: the same device code, qv2x.h)
-        return self._post("fused", L.ptr(codes), agent_stride, level_stride, None, pairwise, [0], [n_agents], ego, own_codes, n_own)
-
-    def single_preds(self, codes, n_agents: int) -> dict:
-        """``*_preds_single`` (heter_model_baseline.py:224-230): the per-agent heads on each agent's own decoded feature."""
-        if self.heads_single is None:
-            return {}
-        return split_heads(self._decode_heads_single(codes, n_agents), self.heads_single.splits, "_single")
-
     def _shared_features(self, shrinker_out, n_total: int):
         """no codebook: the fp32 shared feature [n, H*W, 256] is the dequantized shrinker output"""
         q = self.final.out_q
@@ -1193,51 +1318,6 @@ class DeployedModel(nn.Module):
         L.check(self.lib.qv2x_dequant_i8_f32(L.ptr(shrinker_out), n_total, self.fh, self.fw, 256, int(q[1]), float(q[0]), L.ptr(feats),
                                              L.current_stream()), "qv2x_dequant_i8_f32")
         return feats
-
-    # ---- the reference's model contract ----------------------------------------------------------------------
-    @torch.no_grad()
-    def forward(self, data_dict: dict, taps: Optional[dict] = None) -> dict:
-        agents = data_dict["agent_modality_list"]
-        n_total = len(agents)
-        if any(a != "m1" for a in agents):
-            raise NotImplementedError("deployed path: every agent is the LiDAR modality 'm1' (a heterogeneous model deploys as DeployedHeterModel)")
-        enc = self.encode_agents(data_dict["inputs_m1"], n_total, taps)
-        return self.finish(enc, n_total, data_dict, taps)
-
-    @torch.no_grad()
-    def finish(self, enc, n_total: int, data_dict: dict, taps: Optional[dict] = None) -> dict:
-        """a7-a11 on the agents' wire data ``enc`` (code planes u8 [levels, n_total * H*W] in agent order, or the i8 shrinker output of a
-        model without a codebook): decode + warp + fusion per scene, the heads, the ``*_single`` heads."""
-        pairwise, lens = scene_layout(data_dict, n_total)
-        hw = self.fh * self.fw
-        # (no workspace of n_total agents here: a codebook model's post stage only needs the code planes it is handed -- the ego engine of a
-        #  heterogeneous scene never encodes n_total agents itself)
-        feats = None if self.has_codebook else self._shared_features(enc, n_total)
-        form = self._post_form(lens, taps, lambda: self._self_transforms_are_identity(data_dict["pairwise_t_matrix"]))   # (the caller's own tensor object: see there)
-        if form != "tables" and not pairwise.is_cuda:                   # a host tensor (the reference's collate output before to_device): copied here
-            if torch.cuda.is_current_stream_capturing():
-                raise ValueError("pairwise_t_matrix on the host cannot be uploaded during HIP-graph capture: pass a device tensor")
-            pairwise = pairwise.to(self.dev)
-        starts = [sum(lens[:bi]) for bi in range(len(lens))]
-        if self.has_codebook:
-            out = self._post(form, L.ptr(enc), hw, n_total * hw, None, pairwise, [st * hw for st in starts], lens, 0, enc, n_total, taps)
-        else:
-            out = self._post(form, None, 0, 0, feats, pairwise, [st * hw * 256 for st in starts], lens, 0, None, n_total, taps)
-        if taps is not None:
-            taps["codes"] = enc if self.has_codebook else None
-            taps["features"] = feats
-        return out
-
-    # ---- HIP-graph replay of a fixed-shape frame ---------------------------------------------------------------
-    def capture(self, data_dict: dict):
-        """Capture one frame into a HIP graph (``capture_forward``): the returned callable replays it on the same input tensors.
-
-        The graph relies on the resident canvas being clean between calls (``pillars_to_canvas``): every path of this class leaves it
-        so; ``pillars_to_canvas(resident=False)`` refuses to run on a workspace that has such graphs.
-        The pillar count M = ``voxel_features.shape[0]`` is baked into the graph: keep M fixed across replays and pad
-        unused rows with an out-of-range agent index (``voxel_coords[:, 0] = -1``), which ``pfn_scatter_kernel`` drops.
-        ``record_len`` (several scenes per call) must be a CPU tensor: its values shape the launch list."""
-        return capture_forward(self, data_dict)
 
 
 class DeployedHeterModel(nn.Module):

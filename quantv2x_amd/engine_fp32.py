@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .engine import DeployedModel, _dev, _pack_k4p
+from .engine import DeployedPostStage, _Heads, _dev, pillar_inputs
 from .ptq_state import _np, _HEADS, extended_codebook
 
 
@@ -127,37 +127,32 @@ class _F32Deconv:
         self.bias = _dev(state[name + "/bias"].astype(np.float32), dev)
 
 
-class _F32Heads:
-    """cls | reg | dir stacked, output quantizers off (the same ``qv2x_heads_*`` kernels as the W8A8 path)"""
+class Fp32Pfn:
+    """a1 + a2 of an un-quantized state: the folded PFN as the host arrays qv2x_pfn_scatter_f32 takes, and its launch"""
 
-    def __init__(self, state, suffix, dev):
-        ws = [state[h + suffix + "/w"] for h in _HEADS]
-        bs = [state[h + suffix + "/bias"] for h in _HEADS]
-        self.splits = [w.shape[0] for w in ws]
-        self.cout = sum(self.splits)
-        self.cout_pad = (self.cout + 31) // 32 * 32
-        if self.cout_pad > 96:
-            raise NotImplementedError("heads: at most 96 stacked output channels")
-        pad = self.cout_pad - self.cout
-        self.w = _dev(_pack_k4p(np.concatenate(ws + [np.zeros((pad, 256), np.float32)])), dev)
-        self.bias = _dev(np.concatenate(bs + [np.zeros(pad, np.float32)]), dev)
-        self.da = _dev(np.full(self.cout_pad, -1.0, np.float32), dev)
-        self.za = _dev(np.zeros(self.cout_pad, np.float32), dev)
+    def __init__(self, state):
+        f32a = lambda a: (C.c_float * len(a))(*[float(np.float32(v)) for v in a])
+        self.w, self.b = f32a(state["pfn/w"].reshape(-1)), f32a(state["pfn/bias"])
+        self.vox, self.off = f32a(state["meta/voxel"]), f32a(state["meta/offset"])
+
+    def scatter(self, lib, inputs: dict, canvas: torch.Tensor, n_agents: int, ny: int, nx: int):
+        """zero the padded fp32 canvas [n_agents, ny + 2, nx + 2, 64], then PFN + scatter of the pillars into it"""
+        vf, co, npnt = pillar_inputs(inputs)
+        st = L.current_stream()
+        L.check(lib.qv2x_fill_i8(L.ptr(canvas), canvas.numel() * 4, 0, st), "qv2x_fill_i8")
+        L.check(lib.qv2x_pfn_scatter_f32(L.ptr(vf), L.ptr(co), L.ptr(npnt), vf.shape[0], 32, self.w, self.b, self.vox, self.off,
+                                         L.ptr(canvas), n_agents, ny, nx, st), "qv2x_pfn_scatter_f32")
+        return canvas
 
 
-class DeployedFp32Model(DeployedModel):
-    """Same call contract and the same tail (decode + warp + attention, heads, HIP-graph capture, multi-GPU stage interface) as
-    ``DeployedModel``; a1-a6 in fp32."""
-    single_by_tables = single_by_global_tables = False                  # (its own heads: the *_single heads keep the GEMM forms)
+class DeployedFp32Model(DeployedPostStage):
+    """Same call contract and the same post stage (decode + warp + attention, heads, HIP-graph capture, multi-GPU stage interface) as
+    ``DeployedModel``; the agent stage a1-a6 in fp32."""
 
     def __init__(self, state: Dict[str, np.ndarray], device="cuda", emit_single_preds: Optional[bool] = None):
-        nn.Module.__init__(self)
-        self._setup_common(state, device, emit_single_preds)           # metadata, decode table, level blobs (engine.py)
+        super().__init__(state, device, emit_single_preds)             # metadata, decode table, level blobs (engine.py)
         s, dev = state, self.dev
-        self.compress = False
-        f32a = lambda a: (C.c_float * len(a))(*[float(np.float32(v)) for v in a])
-        self.pfn_w, self.pfn_b = f32a(s["pfn/w"].reshape(-1)), f32a(s["pfn/bias"])
-        self.pfn_vox, self.pfn_off = f32a(s["meta/voxel"]), f32a(s["meta/offset"])
+        self.pfn = Fp32Pfn(s)
         self.blocks: List[List[_F32Conv]] = []
         self.deblocks: List[_F32Deconv] = []
         for lvl in range(len(self.layer_nums)):
@@ -169,15 +164,10 @@ class DeployedFp32Model(DeployedModel):
         self.shrink1 = _F32Conv(s, "shrinker_m1.layers.0.double_conv.1", 1, dev)
         if self.shrink1.cout != 256:
             raise NotImplementedError("deployed path expects a 256-channel shared feature")
-        self.heads = _F32Heads(s, "", dev)
-        self.heads_single = _F32Heads(s, "_single", dev) if (self.emit_single and "cls_head_single/w" in s) else None
+        # (no head tables: the *_single heads keep the GEMM forms, single-agent scenes the general path -- DeployedPostStage._set_heads)
+        self._set_heads(_Heads.folded_fp32(s, "", dev),
+                        _Heads.folded_fp32(s, "_single", dev) if (self.emit_single and "cls_head_single/w" in s) else None, tables=False)
         self._bufs: Dict[int, dict] = {}
-        self.chains = [None] * len(self.blocks)
-        self.use_wide_conv = self.batch_deconvs = self.use_chains = False
-
-    def two_stage_supported(self) -> bool:
-        """never: the two-stage encode's candidate stage reads i8 rows, this model's shrinker writes fp32 ones"""
-        return False
 
     # ---- buffers: fp32 NHWC with a zero border ---------------------------------------------------------------------------
     def _workspace(self, n: int) -> dict:
@@ -203,18 +193,7 @@ class DeployedFp32Model(DeployedModel):
 
     # ---- a1 - a6 -------------------------------------------------------------------------------------------------------------
     def pillars_to_canvas(self, inputs: dict, n_agents: int):
-        b = self._workspace(n_agents)
-        st = L.current_stream()
-        vf = inputs["voxel_features"].contiguous()
-        co = inputs["voxel_coords"].to(torch.int32).contiguous()
-        npnt = inputs["voxel_num_points"].to(torch.int32).contiguous()
-        if vf.dtype != torch.float32 or vf.dim() != 3 or tuple(vf.shape[1:]) != (32, 4):
-            raise ValueError("voxel_features must be float32 [M, 32, 4]")
-        canvas = b["canvas"]
-        L.check(self.lib.qv2x_fill_i8(L.ptr(canvas), canvas.numel() * 4, 0, st), "qv2x_fill_i8")
-        L.check(self.lib.qv2x_pfn_scatter_f32(L.ptr(vf), L.ptr(co), L.ptr(npnt), vf.shape[0], 32, self.pfn_w, self.pfn_b, self.pfn_vox,
-                                              self.pfn_off, L.ptr(canvas), n_agents, self.ny, self.nx, st), "qv2x_pfn_scatter_f32")
-        return canvas
+        return self.pfn.scatter(self.lib, inputs, self._workspace(n_agents)["canvas"], n_agents, self.ny, self.nx)
 
     def _gemm(self, fn, layer, x, n, h, w, out, stride, cin0=0, out_c0=0):
         d = L.F32ConvDesc()
@@ -252,6 +231,8 @@ class DeployedFp32Model(DeployedModel):
     def encode_codes(self, n_agents: int, out: Optional[torch.Tensor] = None):
         b = self._workspace(n_agents)
         codes = b["codes"] if out is None else out
+        if codes.dtype != torch.uint8 or not codes.is_contiguous() or codes.numel() != self.levels * n_agents * self.fh * self.fw:
+            raise ValueError("encode_codes: out must be a contiguous uint8 tensor [levels, n_agents, H*W]")
         d = L.EncodeDesc()
         d.n, d.h, d.w, d.levels, d.kc, d.in_zx, d.in_delta, d.segs = n_agents, self.fh, self.fw, self.enc_levels, self.kc, 0, 1.0, self.segs
         L.check(self.lib.qv2x_codebook_encode_f32in(C.byref(d), L.ptr(b["s1"]), self.level_ptrs, L.ptr(codes), L.current_stream()),
@@ -265,6 +246,12 @@ class DeployedFp32Model(DeployedModel):
         if taps is not None:
             taps["canvas"], taps["cat"] = canvas, b["cat"]
         return self.encode_codes(n_agents) if self.has_codebook else b["s1"]
+
+    def encode_into(self, inputs: dict, frames: int, codes_out: torch.Tensor):
+        """a1-a6 for ``frames`` frames of ONE agent (batch index = frame); codes u8 [levels, frames, H*W] written to ``codes_out``."""
+        self.pillars_to_canvas(inputs, frames)
+        self.run_plan(frames)
+        return self.encode_codes(frames, out=codes_out)
 
     def _shared_features(self, shrinker_out, n_total: int):
         # a copy, not arithmetic: the interior of the padded fp32 tensor as contiguous rows

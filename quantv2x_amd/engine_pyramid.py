@@ -20,8 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .engine import (_ConvLayer, _DeconvLayer, _Heads, _dev, _pack_k4p, assemble_heter_codes, capture_forward, decode_tables, scene_layout,
-                     split_heads, wave_section)
+from .engine import (_ConvLayer, _DeconvLayer, _Heads, _dev, _pack_k4p, _pairwise_from_poses, assemble_heter_codes, capture_forward,
+                     codebook_constants, pfn_params, pillar_inputs, scene_layout, split_heads)
 
 
 def _q(state, name):
@@ -156,19 +156,7 @@ class DeployedPyramidModel(nn.Module):
         self.ratio = float(s["meta/discrete_ratio"])
         self.has_codebook = bool(s["meta/has_codebook"])            # heter_pyramid_collab_mc (LiDAROnly/lidar_pyramid.yaml): no codebook
 
-        n = "encoder_m1.pillar_vfe.pfn_layers.0.linear"
-        wq = ((s[n + "/w_code"].astype(np.float32) - s[n + "/w_zp"].astype(np.float32)[:, None]) * s[n + "/w_delta"].astype(np.float32)[:, None]).astype(np.float32)
-        if wq.shape != (64, 10):
-            raise NotImplementedError("deployed PFN expects Linear(10 -> 64)")
-        p = L.PfnParams()
-        p.w[:] = wq.reshape(-1).tolist()
-        p.b[:] = s[n + "/bias"].astype(np.float32).tolist()
-        p.d1, p.z1 = float(np.float32(s[n + "/a_delta"])), float(s[n + "/a_zp"])
-        p.d2, p.z2 = float(np.float32(s["pfn/a2_delta"])), float(s["pfn/a2_zp"])
-        p.vox[:] = [float(np.float32(v)) for v in s["meta/voxel"]]
-        p.off[:] = [float(np.float32(v)) for v in s["meta/offset"]]
-        self.pfn = p
-        q = (p.d2, int(p.z2))
+        self.pfn, q = pfn_params(s)
 
         # ---- the agent's ResNet level ------------------------------------------------------------------------------------------
         nums, strides = [int(v) for v in s["meta/layer_nums"]], [int(v) for v in s["meta/layer_strides"]]
@@ -179,25 +167,13 @@ class DeployedPyramidModel(nn.Module):
             self.agent_blocks.append(blk)
             q = blk.out_q
         self.agent_q = q
-        # ---- codebook (D = 64: its own encode kernel; other widths run the 256-wide one on zero-padded heads, see _level_blob) --
+        # ---- codebook (D = 64: its own encode kernel; other widths run the 256-wide one on zero-padded heads, engine.level_blob_host) --
         self.native64 = True
         if self.has_codebook:
-            # (seg_num > 1: the extended codebook [m * kc][D]; ``levels`` counts code planes = residual levels * m -- engine.py)
-            self.enc_levels, self.segs = int(s["meta/codebook_levels"]), int(s.get("meta/codebook_segs", 1))
-            self.levels = self.enc_levels * self.segs
-            self.ke, self.D = (int(v) for v in s["codebook/0/codebook"].shape)
-            self.kc = self.ke // self.segs
-            if self.D > 256 or self.D % 4 or self.agent_blocks[-1].cout != self.D:
-                raise NotImplementedError("deployed Pyramid codebook: width <= 256 equal to the agent feature's channels")
+            c = codebook_constants(self.lib, s, dev, self._refuse_codebook)
+            self.enc_levels, self.segs, self.levels, self.ke, self.kc, self.D = c.enc_levels, c.segs, c.levels, c.ke, c.kc, c.D
+            self.lut, self.lut_bias, self.level_blobs, self.level_ptrs = c.lut, c.lut_bias, c.level_blobs, c.level_ptrs
             self.native64 = self.D == 64
-            if self.segs > 1 and self.D not in (64, 256):
-                raise NotImplementedError("deployed Pyramid codebook: seg_num > 1 with a 64- or 256-wide codebook (other widths are zero-padded "
-                                          "to 256, which moves the segment boundaries)")
-            lut, lut_bias = decode_tables(s, self.enc_levels, self.D)
-            lut = lut.reshape(self.levels, self.kc, self.D)
-            self.lut, self.lut_bias = _dev(lut, dev), _dev(lut_bias, dev)
-            self.level_blobs = [self._level_blob(l) for l in range(self.enc_levels)]
-            self.level_ptrs = (C.c_void_p * self.enc_levels)(*[b.data_ptr() for b in self.level_blobs])
         # ---- the pyramid: ResNeXt levels, occupancy heads, deblocks -------------------------------------------------------------------
         p_nums, p_strides = [int(v) for v in s["meta/pyramid_layer_nums"]], [int(v) for v in s["meta/pyramid_layer_strides"]]
         self.ups = [int(v) for v in s["meta/upsample_strides"]]
@@ -232,39 +208,12 @@ class DeployedPyramidModel(nn.Module):
         self.fuse_blocks = True              # stride-1 bottlenecks with an identity shortcut as ONE launch (csrc/bottleneck_i8.hip)
         self.fuse_planes = (64, 128)
 
-    # ------------------------------------------------------------------------------------------------------------------------------
-    def _level_blob(self, l: int) -> torch.Tensor:
-        """One level's heads in the layout of the encode kernel: the native 64-wide one (qv2x_codebook_encode64_f32), or -- other widths
-        -- zero-padded to the 256-wide kernel's (every extra term of every fma chain is 0 * 0 and the padded |.|^2 chains are exactly 0,
-        so the codes equal a native evaluation bit for bit)."""
-        s, kc, D = self.state, self.ke, self.D                             # (kc: rows of the extended codebook)
-        g = lambda n: s[f"codebook/{l}/{n}"].astype(np.float32)
-        W = 64 if self.native64 else 256
-
-        def pw(w):
-            out = np.zeros((W, W), np.float32); out[:D, :D] = w; return _pack_k4p(out)
-
-        def pb(b):
-            out = np.zeros(W, np.float32); out[:D] = b; return out
-        last = f"codebook/{l}/lhead_w" not in s
-        cb = np.zeros((kc, W), np.float32); cb[:, :D] = g("codebook")
-        parts = [pw(g("stage_w")), pb(g("stage_b")), pw(g("qhead_w")), pb(g("qhead_b")),
-                 np.zeros((W // 4, W, 4), np.float32) if last else pw(g("lhead_w")), np.zeros(W, np.float32) if last else pb(g("lhead_b")),
-                 _pack_k4p(cb), cb, np.zeros(kc, np.float32)]
-        flat = np.concatenate([p.reshape(-1) for p in parts])
-        wg = flat.size
-        if not self.native64:                                              # the 256-wide kernel's blob carries the wave form's section too
-
-            def full(w):
-                out = np.zeros((W, W), np.float32); out[:D, :D] = w; return out
-            flat = np.concatenate([flat, wave_section(full(g("stage_w")), full(g("qhead_w")), np.zeros((W, W), np.float32) if last else full(g("lhead_w")), cb, self.segs)])
-        floats, c2fn = ((self.lib.qv2x_codebook64_level_floats, self.lib.qv2x_codebook64_c2_f32) if self.native64
-                        else (self.lib.qv2x_codebook_level_floats, self.lib.qv2x_codebook_c2_f32))
-        assert flat.size == floats(kc)
-        blob = _dev(flat, self.dev)
-        cb_off = wg - kc - kc * W
-        L.check(c2fn(C.c_void_p(blob.data_ptr() + 4 * cb_off), kc, C.c_void_p(blob.data_ptr() + 4 * (wg - kc)), L.current_stream()), "codebook c2")
-        return blob
+    def _refuse_codebook(self, ke, kc, D, segs):
+        if D > 256 or D % 4 or self.agent_blocks[-1].cout != D:
+            raise NotImplementedError("deployed Pyramid codebook: width <= 256 equal to the agent feature's channels")
+        if segs > 1 and D not in (64, 256):
+            raise NotImplementedError("deployed Pyramid codebook: seg_num > 1 with a 64- or 256-wide codebook (other widths are zero-padded "
+                                      "to 256, which moves the segment boundaries)")
 
     def _padded(self, n, h, w, c, zp):
         t = torch.empty((n, h + 2, w + 2, c), dtype=torch.int8, device=self.dev)
@@ -433,11 +382,7 @@ class DeployedPyramidModel(nn.Module):
     def pillars_to_canvas(self, inputs: dict, n: int):
         b = self._agent_ws(n)
         st = L.current_stream()
-        vf = inputs["voxel_features"].contiguous()
-        co = inputs["voxel_coords"].to(torch.int32).contiguous()
-        npnt = inputs["voxel_num_points"].to(torch.int32).contiguous()
-        if vf.dtype != torch.float32 or vf.dim() != 3 or tuple(vf.shape[1:]) != (32, 4):
-            raise ValueError("voxel_features must be float32 [M, 32, 4]")
+        vf, co, npnt = pillar_inputs(inputs)
         canvas = b["canvas"]
         L.check(self.lib.qv2x_fill_i8(L.ptr(canvas), canvas.numel(), int(self.pfn.z2) - 128, st), "qv2x_fill_i8")
         L.check(self.lib.qv2x_pfn_scatter_i8(L.ptr(vf), L.ptr(co), L.ptr(npnt), vf.shape[0], 32, C.byref(self.pfn), L.ptr(canvas), n, self.ny, self.nx, st),
@@ -617,9 +562,7 @@ class DeployedPyramidModel(nn.Module):
         """``encode_features`` for ``frames`` frames of ONE agent (batch index = frame) into ``codes_out`` u8 [levels, frames, H*W]."""
         return self.encode_features(inputs, frames, out=codes_out)
 
-    def pairwise_from_poses(self, gathered: torch.Tensor, world: int, agent_stride: int, pose_offset: int, max_cav: int, out: torch.Tensor):
-        L.check(self.lib.qv2x_pairwise_from_poses_f64(L.ptr(gathered), world, agent_stride, pose_offset, max_cav, L.ptr(out), L.current_stream()),
-                "qv2x_pairwise_from_poses_f64")
+    pairwise_from_poses = _pairwise_from_poses
 
     def fuse_frames_and_heads(self, gathered: torch.Tensor, agent_stride: int, level_stride: int, frame_stride: int, pairwise: torch.Tensor,
                               n_agents: int, ego: int, own_codes: Optional[torch.Tensor], frames: int) -> dict:

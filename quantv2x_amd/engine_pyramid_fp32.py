@@ -17,8 +17,8 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .engine import _dev, decode_tables, scene_layout, split_heads
-from .engine_fp32 import _F32Heads, _fold, pack_k8
+from .engine import _Heads, _dev, codebook_constants, scene_layout, split_heads
+from .engine_fp32 import Fp32Pfn, _fold, pack_k8
 from .ptq_state import _HEADS, _np, extended_codebook
 
 
@@ -134,9 +134,7 @@ class DeployedPyramidFp32Model(nn.Module):
         self.hm, self.wm = (float(v) for v in s["meta/HW_metres"])
         self.ratio = float(s["meta/discrete_ratio"])
         self.has_codebook = bool(s["meta/has_codebook"])
-        f32a = lambda a: (C.c_float * len(a))(*[float(np.float32(v)) for v in a])
-        self.pfn_w, self.pfn_b = f32a(s["pfn/w"].reshape(-1)), f32a(s["pfn/bias"])
-        self.pfn_vox, self.pfn_off = f32a(s["meta/voxel"]), f32a(s["meta/offset"])
+        self.pfn = Fp32Pfn(s)
         self.agent_stride = int(s["meta/layer_strides"][0])
         self.p_strides = [int(v) for v in s["meta/pyramid_layer_strides"]]
         self.ups = [int(v) for v in s["meta/upsample_strides"]]
@@ -153,19 +151,9 @@ class DeployedPyramidFp32Model(nn.Module):
             self.agent_blocks.append(blk)
         self.D = self.agent_blocks[-1]["conv2"].cout
         if self.has_codebook:
-            self.enc_levels, self.segs = int(s["meta/codebook_levels"]), int(s.get("meta/codebook_segs", 1))
-            self.levels = self.enc_levels * self.segs                  # code planes (engine.py)
-            self.ke, d = (int(v) for v in s["codebook/0/codebook"].shape)
-            self.kc = self.ke // self.segs
-            if d != 64 or self.D != 64:
-                raise NotImplementedError("deployed fp32 Pyramid codebook: the 64-wide one")
-            lut, lut_bias = decode_tables(s, self.enc_levels, 64)
-            lut = lut.reshape(self.levels, self.kc, 64)
-            self.lut, self.lut_bias = _dev(lut, dev), _dev(lut_bias, dev)
-            from .engine_pyramid import DeployedPyramidModel
-            self.native64 = True
-            self.level_blobs = [DeployedPyramidModel._level_blob(self, l) for l in range(self.enc_levels)]
-            self.level_ptrs = (C.c_void_p * self.enc_levels)(*[b.data_ptr() for b in self.level_blobs])
+            c = codebook_constants(self.lib, s, dev, self._refuse_codebook)
+            self.enc_levels, self.segs, self.levels, self.ke, self.kc = c.enc_levels, c.segs, c.levels, c.ke, c.kc
+            self.lut, self.lut_bias, self.level_blobs, self.level_ptrs = c.lut, c.lut_bias, c.level_blobs, c.level_ptrs
         self.pyr_blocks, self.occ, self.deblocks = [], [], []
         for lvl, nb in enumerate(int(v) for v in s["meta/pyramid_layer_nums"]):
             blocks = []
@@ -193,8 +181,12 @@ class DeployedPyramidFp32Model(nn.Module):
         self.cat_channels = sum(d.cout for d in self.deblocks)
         w, bi = g("shrink_conv.layers.0.double_conv.0"); self.shrink0 = _G("shrink_conv.layers.0.double_conv.0", dense3x3(w), bi, dev, w.shape[1], w.shape[0])
         w, bi = g("shrink_conv.layers.0.double_conv.1"); self.shrink1 = _G("shrink_conv.layers.0.double_conv.1", dense3x3(w), bi, dev, w.shape[1], w.shape[0])
-        self.heads = _F32Heads(s, "", dev)
+        self.heads = _Heads.folded_fp32(s, "", dev)
         self._bufs: Dict[tuple, dict] = {}
+
+    def _refuse_codebook(self, ke, kc, D, segs):
+        if D != 64 or self.D != 64:
+            raise NotImplementedError("deployed fp32 Pyramid codebook: the 64-wide one")
 
     # ---- buffers: fp32 NHWC with a zero border --------------------------------------------------------------------------------------
     def _z(self, n, h, w, c):
@@ -245,17 +237,7 @@ class DeployedPyramidFp32Model(nn.Module):
     @torch.no_grad()
     def agent_features(self, inputs: dict, n: int, nb: int = 1, taps: Optional[dict] = None):
         b = self._ws(n, nb)
-        st = L.current_stream()
-        vf = inputs["voxel_features"].contiguous()
-        co = inputs["voxel_coords"].to(torch.int32).contiguous()
-        npnt = inputs["voxel_num_points"].to(torch.int32).contiguous()
-        if vf.dtype != torch.float32 or vf.dim() != 3 or tuple(vf.shape[1:]) != (32, 4):
-            raise ValueError("voxel_features must be float32 [M, 32, 4]")
-        canvas = b["canvas"]
-        L.check(self.lib.qv2x_fill_i8(L.ptr(canvas), canvas.numel() * 4, 0, st), "qv2x_fill_i8")
-        L.check(self.lib.qv2x_pfn_scatter_f32(L.ptr(vf), L.ptr(co), L.ptr(npnt), vf.shape[0], 32, self.pfn_w, self.pfn_b, self.pfn_vox, self.pfn_off,
-                                              L.ptr(canvas), n, self.ny, self.nx, st), "qv2x_pfn_scatter_f32")
-        x, h, w = canvas, self.ny, self.nx
+        x, h, w = self.pfn.scatter(self.lib, inputs, b["canvas"], n, self.ny, self.nx), self.ny, self.nx
         for i, blk in enumerate(self.agent_blocks):
             out = b["feat"] if i == len(self.agent_blocks) - 1 else b["x"][i % 2]
             self._gemm(blk["conv1"], x, n, h, w, b["c1"])

@@ -69,6 +69,42 @@ def test_fp32_no_codebook_single_class():
     np.testing.assert_allclose(got["preds_tensor"].cpu().numpy(), want["preds_tensor"], rtol=2e-4, atol=2e-4)
 
 
+def test_fp32_engine_has_the_multi_gpu_stage_interface():
+    """The fp32 engine behind the multi-GPU driver, a world of one: ``encode_into`` writes the code planes ``encode_agents`` returns, and
+    ``AgentShardedModel.forward`` is the engine's own forward bit for bit.  Both routes run the same kernels: the tiny map is below
+    ``fuse_heads_min_tiles`` and an fp32 engine builds no head tables, so both take the "fused" form; the only transform of a world of one
+    is the identity, which is also the scene's ``pairwise_t_matrix[0, 0, 0]``."""
+    import socket
+    import torch.distributed as dist
+    from quantv2x_amd import synth
+    from quantv2x_amd.dist import AgentShardedModel
+    from quantv2x_amd.engine import deploy
+    eng = deploy(build_plugin("tiny"))
+    dd = synth.scene_to_torch(scene_np(1), "cuda")
+    inputs = dd["inputs_m1"]
+    assert torch.equal(dd["pairwise_t_matrix"][0, 0, 0].cpu(), torch.eye(4, dtype=dd["pairwise_t_matrix"].dtype))
+    assert eng.table_heads is None and not eng.single_by_tables and not eng.single_by_global_tables
+    levels, hw = eng.wire_shape()
+    want_codes = eng.encode_agents(inputs, 1).clone()
+    assert want_codes.dtype == torch.uint8 and want_codes.numel() == levels * hw
+    out = torch.full((levels, 1, hw), 255, dtype=torch.uint8, device="cuda")
+    eng.encode_into(inputs, 1, out)
+    assert torch.equal(out.view(-1), want_codes.view(-1))
+    want = {k: v.clone() for k, v in eng(dd).items()}
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)   # (a world of one: its exchange is a copy)
+    try:
+        got = AgentShardedModel(eng, graphs=False).forward(inputs, torch.eye(4, dtype=torch.float64, device="cuda"))
+    finally:
+        dist.destroy_process_group()
+    torch.cuda.synchronize()
+    assert set(got) == set(want) and "preds_tensor" in want
+    for k in want:
+        assert got[k].dtype == want[k].dtype and torch.equal(got[k], want[k]), k
+
+
 def test_v2xreal_fp32_frame_exact_and_timed():
     """configs[1] shape in fp32: exact vs the oracle; prints the fp32-path frame time next to the W8A8 one (the reference's claim:
     'W8A8 quantization for substantial speedup')."""
