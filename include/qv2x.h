@@ -42,7 +42,8 @@ const char* qv2x_last_error(void);
  * qv2x_codebook_encode_candidates_seg_i8 added and qv2x_codebook_encode_listed_f32 widened to seg_num 2 / dict_size 256, no struct changed;
  * 9 = qv2x_voxelize_batch_f32 / qv2x_postprocess_batch_f32 and their workspace queries added, no struct changed.  The detection-evaluation
  * entries (qv2x_eval_desc, qv2x_eval_workspace_bytes, qv2x_eval_tp_fp_f32) and the ground-truth entry (qv2x_gt_desc, qv2x_gt_boxes_f32)
- * joined under 9: nothing that existed changed, and a caller that needs them finds out by looking the symbol up. */
+ * joined under 9: nothing that existed changed, and a caller that needs them finds out by looking the symbol up.  So did the PTQ
+ * range search (qv2x_range_search_desc, qv2x_range_search_workspace_bytes, qv2x_range_search_f32): additions only, the value stays 9. */
 #define QV2X_ABI_VERSION 9
 int qv2x_version(void);            /* == QV2X_ABI_VERSION of the library's own build */
 
@@ -820,6 +821,39 @@ typedef struct {
 int qv2x_gt_boxes_f32(const qv2x_gt_desc* desc /* host */, const float* boxes, const uint8_t* mask, const int32_t* ids, const float* transforms,
                       const int32_t* agent_counts, float* gt_corners, int32_t* gt_labels, int32_t* gt_ids, int32_t* gt_counts,
                       int32_t* gt_totals, void* stream);
+
+/* ---- PTQ calibration: the MSE range search of UniformAffineQuantizer as one evaluation of every candidate -------------------------------
+ * perform_2D_search / perform_1D_search of the reference (opencood/quant/quant_layer.py:201-254) walk their candidates in a Python loop,
+ * one pass over the tensor and about ten torch launches per candidate.  Here the K (delta, zero point) pairs of a search are a table the
+ * caller builds up front (quantv2x_amd/calibration.py: candidate_table) and one call scores them all.
+ *   value      for candidate k and channel c, with d = delta[k][c], z = zp[k][c]:
+ *                  q = (clamp(rint(x / d) + z, 0, n_levels - 1) - z) * d
+ *              rint(x / d) is the integer torch.round(x / d) gives in fp32 (IEEE division, ties to even); the kernel multiplies by
+ *              fl(1 / d) and redoes the division where that product lies within 3e-4 of a half-integer (below |x / d| = 1100 the two
+ *              differ by < 2e-4; above it both clamp: z and n_levels - 1 are <= 255).
+ *   loss       loss[k][c] = mean over the channel of |x - q|^2.4.  Each term is fp32: e = |fma(z - code, d, x)| -- the exact difference
+ *              rounded once -- and e * e * exp2(0.4f * log2(e)) with the hardware's log2 / exp2 (e == 0 gives 0).  Every term enters an
+ *              fp64 sum in element order; a long row is cut into slices of whole staging chunks, the slices' fp64 sums are added in slice
+ *              order and divided by per_channel.  The slicing depends on the descriptor alone, there are no floating-point atomics: the
+ *              same call returns the same bits every time.  Against the formula's exact value the only deviation is the per-term error
+ *              of the power (about 1e-6 relative).
+ *   best       best[c] = the FIRST k with the least loss[k][c]: the reference's strict `score < best_score` walk in candidate order.
+ *              (A channel whose losses are all NaN reports 0.)
+ *   x f32 [channels][per_channel]; delta, zp f32 [candidates][channels], delta > 0 (calculate_qparams gives >= 1e-8), zp an integer in
+ *   0..n_levels - 1 stored as f32; loss f64 [candidates][channels] (may be NULL); best i32 [channels]; workspace: 8-byte aligned device
+ *   memory of qv2x_range_search_workspace_bytes(desc) bytes (the slices' partial sums).
+ * All data pointers are device pointers.  Two launches, asynchronous on `stream`, nothing allocated or copied: HIP-graph capturable.
+ * QV2X_EINVAL before any GPU call for a null required pointer or a descriptor outside the limits below (the workspace query returns -1). */
+typedef struct {
+    int32_t channels;        /* >= 1 */
+    int32_t candidates;      /* 1..65536 */
+    int32_t n_levels;        /* 4..256 */
+    int32_t reserved;        /* 0 */
+    int64_t per_channel;     /* >= 1 elements per channel */
+} qv2x_range_search_desc;
+int64_t qv2x_range_search_workspace_bytes(const qv2x_range_search_desc* desc /* host */);
+int qv2x_range_search_f32(const qv2x_range_search_desc* desc /* host */, const float* x, const float* delta, const float* zp, double* loss,
+                          int32_t* best, void* workspace, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -34,9 +34,16 @@ def lp_loss(pred, tgt, p=2.0, reduction='none'):
 
 
 class UniformAffineQuantizer(nn.Module):
+    # who walks the candidates of the MSE search: 'torch' = the loops below; 'hip' = one qv2x_range_search_f32 call on the same table
+    # (quantv2x_amd/calibration.py) when the observed tensor lives on the GPU.  Opt-in, per instance or through set_search_backend().
+    search_backend = 'torch'
+
     def __init__(self, n_bits: int = 8, symmetric: bool = False, channel_wise: bool = False,
-                 scale_method: str = 'mse', leaf_param: bool = False, prob: float = 1.0):
+                 scale_method: str = 'mse', leaf_param: bool = False, prob: float = 1.0, search_backend: str = None):
         super().__init__()
+        if search_backend is not None:
+            assert search_backend in ('torch', 'hip'), 'search backend not supported'
+            self.search_backend = search_backend
         self.sym = symmetric
         if self.sym:
             raise NotImplementedError
@@ -122,11 +129,21 @@ class UniformAffineQuantizer(nn.Module):
             return lo, hi
         return tuple(torch.aminmax(x))
 
+    def _search_on_gpu(self, x, mode):
+        """the search as one kernel call (``search_backend == 'hip'``, MSE, a GPU tensor), else None"""
+        if self.search_backend != 'hip' or self.scale_method != 'mse' or not x.is_cuda:
+            return None
+        from ...calibration import gpu_range_search
+        return gpu_range_search(x, self.n_bits, self.channel_wise, mode, self.num)
+
     def perform_2D_search(self, x):
         """Search (range width, zero point) minimising the L2.4 error (reference ``:202-234``)."""
         x_min, x_max = self._observed_range(x, include_zero=True)
         if self.scale_method == 'minmax':
             return x_min, x_max
+        on_gpu = self._search_on_gpu(x, '2d')
+        if on_gpu is not None:
+            return on_gpu
         span = x_max - x_min
         best = torch.zeros_like(x_min) + 1e+10
         best_min, best_max = x_min.clone(), x_max.clone()
@@ -146,6 +163,9 @@ class UniformAffineQuantizer(nn.Module):
         x_min, x_max = self._observed_range(x, include_zero=False)
         if self.scale_method == 'minmax':
             return x_min, x_max
+        on_gpu = self._search_on_gpu(x, self.one_side_dist if self.one_side_dist in ('pos', 'neg') else 'sym')
+        if on_gpu is not None:
+            return on_gpu
         reach = torch.max(x_min.abs(), x_max)
         best = torch.zeros_like(x_min) + 1e+10
         best_min, best_max = x_min.clone(), x_max.clone()

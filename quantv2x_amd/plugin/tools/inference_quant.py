@@ -13,16 +13,20 @@ import torch
 from ..quant import QuantModel, UniformAffineQuantizer, set_weight_quantize_params
 
 
-def quant_params(n_bits_w=8, n_bits_a=8, scale_method="minmax", prob=0.5):
+def quant_params(n_bits_w=8, n_bits_a=8, scale_method="minmax", prob=0.5, search_backend="torch"):
+    """``search_backend='hip'``: the MSE range searches of GPU tensors run as one kernel call each (quantv2x_amd/calibration.py); the
+    default leaves the dicts as the reference's driver builds them."""
     wq = dict(n_bits=n_bits_w, channel_wise=True, scale_method=scale_method)
     aq = dict(n_bits=n_bits_a, channel_wise=False, scale_method=scale_method, leaf_param=True, prob=prob)
+    if search_backend != "torch":
+        wq["search_backend"] = aq["search_backend"] = search_backend
     return wq, aq
 
 
-def wrap(model, scale_method="minmax", n_bits_w=8, n_bits_a=8, first_last_8bit=False):
+def wrap(model, scale_method="minmax", n_bits_w=8, n_bits_a=8, first_last_8bit=False, search_backend="torch"):
     """``first_last_8bit``: ``set_first_last_layer_to_8bit`` (quant_model.py:115-127) between the wrap and the weight-quantizer
     initialisation, where the driver has it (inference_quant.py:248-250) -- the usual companion of ``--n_bits_w 4``."""
-    wq, aq = quant_params(n_bits_w, n_bits_a, scale_method=scale_method)
+    wq, aq = quant_params(n_bits_w, n_bits_a, scale_method=scale_method, search_backend=search_backend)
     qt = QuantModel(model, wq, aq).eval()
     if first_last_8bit:
         qt.set_first_last_layer_to_8bit()
@@ -50,11 +54,11 @@ def calibrate_minmax(qt, batches, seed=0):
 
 
 # ---- reconstruction path of the driver (inference_quant.py:236-243, 268-322) ------------------------------------------------
-def wrap_pair(model, scale_method="minmax", prob=0.5):
+def wrap_pair(model, scale_method="minmax", prob=0.5, search_backend="torch"):
     """``(fp_model, qt_model)`` as the driver builds them: the fp twin keeps its BatchNorm layers (``is_fusing=False``) and runs
     with quantization off -- its BN statistics drive the distribution correction -- the quantized one is folded."""
     import copy
-    wq, aq = quant_params(scale_method=scale_method, prob=prob)
+    wq, aq = quant_params(scale_method=scale_method, prob=prob, search_backend=search_backend)
     fp = QuantModel(copy.deepcopy(model), wq, aq, is_fusing=False).eval()
     fp.set_quant_state(False, False)
     qt = QuantModel(model, wq, aq).eval()
