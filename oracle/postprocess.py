@@ -17,7 +17,9 @@ one CAV (intermediate fusion: ``data_dict`` holds the ego only):
 
 Pinned against the reference by ``tests/golden/postprocess.npz`` for everything except the polygon IoU itself: the
 reference computes it with shapely (absent here, un-vendored: parity unpinned for that function); this file uses
-Sutherland-Hodgman clipping of the two convex quadrilaterals in float64.
+Sutherland-Hodgman clipping of the two convex quadrilaterals in float64.  tests/test_postprocess_cases_cpu.py holds that clipping against
+``inter_area_by_vertices`` of tests/_postprocess_cases.py, which does not clip (vertex sets + shoelace), and tests/test_hip_postprocess_cases.py
+runs this file against csrc/postprocess.hip on planted edge cases, stage by stage.
 """
 from __future__ import annotations
 
@@ -126,7 +128,10 @@ def quad_intersection_area(p, q):
             s += x0 * y1 - x1 * y0
         return 0.5 * s
     clip = [tuple(map(float, v)) for v in q]
-    if signed_area(clip) < 0:
+    qa = signed_area(clip)
+    if qa == 0:                                                    # a clip polygon without area (a point: four zero-length edges clip nothing)
+        return 0.0
+    if qa < 0:
         clip = clip[::-1]
     out = [tuple(map(float, v)) for v in p]
     for i in range(4):

@@ -17,6 +17,8 @@
 //   6. range mask on all eight corners (box_utils.py:384-421), outputs compacted in score order.
 // The reference's polygon IoU is shapely's (un-vendored): oracle/postprocess.py restates it with the same clipping as
 // here; everything else is pinned against the reference by tests/golden/postprocess.npz and postprocess_mc.npz.
+// tests/test_hip_postprocess_cases.py drives every stage below on planted edge cases (tests/_postprocess_cases.py), and
+// tests/test_postprocess_cases_cpu.py holds the shared clipping against a reference that does not clip (inter_area_by_vertices).
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"

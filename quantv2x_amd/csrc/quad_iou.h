@@ -1,6 +1,7 @@
 // Area of two convex quadrilaterals and of their intersection in fp64: what the rotated NMS (postprocess.hip) and the detection evaluator
 // (eval.hip) both call an IoU.  The reference takes these areas from shapely (un-vendored); oracle/postprocess.py restates the clipping
-// below operation for operation, and the post-process suites hold the two bit-equal.
+// below operation for operation, and the post-process suites hold the two bit-equal; tests/test_postprocess_cases_cpu.py holds the
+// clipping itself against a reference that does not clip.
 #pragma once
 #include "common.h"
 
@@ -10,6 +11,7 @@ namespace qv2x {
 static __device__ double quad_inter_area(const double (&p)[4][2], const double (&q)[4][2]) {
     double qa = 0.0;
     for (int i = 0; i < 4; ++i) qa += q[i][0] * q[(i + 1) & 3][1] - q[(i + 1) & 3][0] * q[i][1];
+    if (qa == 0.0) return 0.0;                                     // a clip polygon without area (a point: four zero-length edges clip nothing)
     const bool rev = qa < 0.0;                                     // clip polygon walked counter-clockwise
     double cur[8][2], nxt[8][2];
     int n = 4;

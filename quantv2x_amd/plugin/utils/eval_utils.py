@@ -49,7 +49,10 @@ def quad_inter_area(p, q):
     """area of the intersection of two convex quadrilaterals (float64, any orientation): Sutherland-Hodgman, the operations of
     csrc/quad_iou.h in the same order"""
     clip = [(float(v[0]), float(v[1])) for v in q]
-    if _signed_area2(clip) < 0.0:
+    qa = _signed_area2(clip)
+    if qa == 0.0:                                                  # a clip polygon without area (a point: four zero-length edges clip nothing)
+        return 0.0
+    if qa < 0.0:
         clip = clip[::-1]
     out = [(float(v[0]), float(v[1])) for v in p]
     for i in range(4):
