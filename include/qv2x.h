@@ -855,6 +855,58 @@ int64_t qv2x_range_search_workspace_bytes(const qv2x_range_search_desc* desc /* 
 int qv2x_range_search_f32(const qv2x_range_search_desc* desc /* host */, const float* x, const float* delta, const float* zp, double* loss,
                           int32_t* best, void* workspace, void* stream);
 
+/* ---- camera agents: lift-splat BEV pooling (get_geometry + voxel_pooling of LiftSplatShoot) as a plan and a splat -----------------------
+ * The reference (opencood/models/lift_splat_shoot.py:89-181; quant_block.py:874-965 quantizes the same module) forms the outer product of
+ * depth distribution and image features for every frustum point, sorts it by cell, takes differences of a running total over ALL points
+ * (QuickCumsum) and scatters.  Here a PLAN holds every frustum point's cell and the points grouped by cell -- it depends on the camera
+ * matrices alone, which a vehicle's rig does not change from frame to frame -- and a SPLAT sums softmax(depth)[p] * feat[pixel(p)][c] per
+ * cell.  quantv2x_amd/lift_splat.py states both in float64 (geometry_statement, cells_statement, splat_statement); DESIGN.md section 13.
+ *   point      p = (((b * views + n) * depth_bins + d) * fh + h) * fw + w, the flat index of [samples][views][depth_bins][fh][fw]
+ *   geometry   from the f32 inputs in fp64, no fused multiply-add, rounded to f32 once per coordinate:
+ *                  q = frustum[d][h][w] - post_trans;   u_i = (Pinv[i][0] q0 + Pinv[i][1] q1) + Pinv[i][2] q2
+ *                  w = (u0 * u2, u1 * u2, u2);          g_i = ((M[i][0] w0 + M[i][1] w1) + M[i][2] w2) + trans_i
+ *              Pinv = inverse(post_rots), M = rots * inverse(intrins) with M[i][j] = (R[i][0] K[0][j] + R[i][1] K[1][j]) + R[i][2] K[2][j];
+ *              a 3x3 inverse is adjugate / determinant: c00 = a11 a22 - a12 a21, c01 = a02 a21 - a01 a22, c02 = a01 a12 - a02 a11,
+ *              c10 = a12 a20 - a10 a22, c11 = a00 a22 - a02 a20, c12 = a02 a10 - a00 a12, c20 = a10 a21 - a11 a20, c21 = a01 a20 - a00 a21,
+ *              c22 = a00 a11 - a01 a10, det = (a00 c00 + a01 c10) + a02 c20, inverse[i][j] = cij / det.
+ *   cell       the reference's expression in f32, quirks included: t = (g - fl(bx - dx / 2)) / dx per axis, index = t truncated TOWARD ZERO
+ *              (`.long()`), kept iff 0 <= index < nx on all three axes: a coordinate up to one cell below the range is KEPT, in cell 0.
+ *              A point with a non-finite coordinate is dropped (this project's contract; the reference's result there is undefined).
+ *              cells_out[p] = (iz * nx[1] + iy) * nx[0] + ix, or -1.
+ *   plan       the kept points grouped by (sample, cell), ascending p inside a cell, with a per-cell interval table and the kept count,
+ *              all in the workspace; nothing is read back.
+ *   splat      out [samples][nx[2] * features][nx[1]][nx[0]], channel z * features + c (torch.cat(final.unbind(2), 1)), map [Y][X] (the
+ *              reference's "modify griddify").  out = sum over the cell's points, in plan order, of fl(prob[p] * feat[view(p)][c][h][w])
+ *              accumulated in fp32 from +0: one rounded product and one rounded add per point.  EVERY element of out is written, empty
+ *              cells as +0; the caller does not clear.  No atomics: the same inputs give the same bits on every call and on a graph replay.
+ *              mode QV2X_LSS_LOGITS: prob = softmax of depth over depth_bins, the maximum subtracted, exponentials, sum and quotient in
+ *              fp64, rounded to f32 once.  mode QV2X_LSS_PROBS: prob = depth as given (use_gt_depth's one-hot).
+ *              Against the exact sum the error of an element is at most (n + 2) * 2^-24 * S to first order (n = points of the cell,
+ *              S = sum of |prob * feat| over it).  Non-finite depth or feats: undefined values in the cells they reach, nothing else.
+ *   frustum f32 [depth_bins][fh][fw][3] (u, v, depth); rots, intrins, post_rots f32 [samples * views][3][3]; trans, post_trans f32
+ *   [samples * views][3]; cells_out i32 [points]; depth f32 [samples * views][depth_bins][fh][fw]; feats f32 [samples * views][features][fh][fw];
+ *   workspace: 16-byte aligned device memory of qv2x_lss_workspace_bytes(desc) bytes, the SAME block for the plan and every splat that uses
+ *   it (the splat keeps its probabilities and a pixel-major copy of feats there).  A splat on a workspace that holds no plan of this shape
+ *   writes +0 everywhere.
+ * All data pointers are device pointers.  Asynchronous on `stream`, nothing allocated or copied: HIP-graph capturable.  QV2X_EINVAL before
+ * any GPU call for a null pointer or a descriptor outside the limits below, naming the value (the workspace query returns -1). */
+#define QV2X_LSS_LOGITS 0
+#define QV2X_LSS_PROBS 1
+typedef struct {
+    int32_t samples;         /* B */
+    int32_t views;           /* N cameras per sample; samples * views in 1..64 */
+    int32_t depth_bins;      /* D, 1..128 */
+    int32_t fh, fw;          /* feature map; samples * views * depth_bins * fh * fw (the points) inside int32 */
+    int32_t features;        /* C: a multiple of 8 in 8..256 */
+    int32_t nx[3];           /* cells along x, y, z; samples * nx[0] * nx[1] * nx[2] inside int32 */
+    float dx[3], bx[3];      /* gen_dx_bx's f32 values: cell size (> 0) and centre of the first cell */
+} qv2x_lss_desc;
+int64_t qv2x_lss_workspace_bytes(const qv2x_lss_desc* desc /* host */);
+int qv2x_lss_plan_f32(const qv2x_lss_desc* desc /* host */, const float* frustum, const float* rots, const float* trans, const float* intrins,
+                      const float* post_rots, const float* post_trans, int32_t* cells_out, void* workspace, void* stream);
+int qv2x_lss_splat_f32(const qv2x_lss_desc* desc /* host */, const float* depth, const float* feats, int mode, void* workspace, float* out,
+                       void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -30,6 +30,7 @@ SYMBOLS = [
     "qv2x_voxelize_batch_workspace_bytes", "qv2x_voxelize_batch_f32", "qv2x_postprocess_batch_workspace_bytes", "qv2x_postprocess_batch_f32",
     "qv2x_eval_workspace_bytes", "qv2x_eval_tp_fp_f32", "qv2x_gt_boxes_f32",
     "qv2x_range_search_workspace_bytes", "qv2x_range_search_f32",
+    "qv2x_lss_workspace_bytes", "qv2x_lss_plan_f32", "qv2x_lss_splat_f32",
 ]
 WIRES = {"f32": 0, "u8": 1}     # QV2X_WIRE_F32, QV2X_WIRE_U8
 COMM_ID_BYTES = 128
@@ -130,6 +131,11 @@ class RangeSearchDesc(C.Structure):
     _fields_ = [("channels", C.c_int32), ("candidates", C.c_int32), ("n_levels", C.c_int32), ("reserved", C.c_int32), ("per_channel", C.c_int64)]
 
 
+class LssDesc(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("views", C.c_int32), ("depth_bins", C.c_int32), ("fh", C.c_int32), ("fw", C.c_int32),
+                ("features", C.c_int32), ("nx", C.c_int32 * 3), ("dx", C.c_float * 3), ("bx", C.c_float * 3)]
+
+
 class Qv2xError(RuntimeError):
     pass
 
@@ -212,6 +218,10 @@ def load() -> C.CDLL:
     lib.qv2x_range_search_workspace_bytes.argtypes = [C.POINTER(RangeSearchDesc)]
     lib.qv2x_range_search_workspace_bytes.restype = C.c_int64
     lib.qv2x_range_search_f32.argtypes = [C.POINTER(RangeSearchDesc), vp, vp, vp, vp, vp, vp, vp]
+    lib.qv2x_lss_workspace_bytes.argtypes = [C.POINTER(LssDesc)]
+    lib.qv2x_lss_workspace_bytes.restype = C.c_int64
+    lib.qv2x_lss_plan_f32.argtypes = [C.POINTER(LssDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.qv2x_lss_splat_f32.argtypes = [C.POINTER(LssDesc), vp, vp, C.c_int, vp, vp, vp]
     lib.qv2x_postprocess_workspace_bytes.argtypes = [C.POINTER(PostprocessDesc)]
     lib.qv2x_postprocess_workspace_bytes.restype = C.c_int64
     lib.qv2x_postprocess_f32.argtypes = [C.POINTER(PostprocessDesc), vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
@@ -256,7 +266,7 @@ def load() -> C.CDLL:
     for s in SYMBOLS:
         if s not in ("qv2x_last_error", "qv2x_codebook_level_floats", "qv2x_codebook64_level_floats", "qv2x_voxelize_workspace_bytes", "qv2x_postprocess_workspace_bytes",
                      "qv2x_postprocess_late_workspace_bytes", "qv2x_sp_out_sites_workspace_bytes", "qv2x_voxelize_batch_workspace_bytes",
-                     "qv2x_postprocess_batch_workspace_bytes", "qv2x_eval_workspace_bytes", "qv2x_range_search_workspace_bytes"):
+                     "qv2x_postprocess_batch_workspace_bytes", "qv2x_eval_workspace_bytes", "qv2x_range_search_workspace_bytes", "qv2x_lss_workspace_bytes"):
             getattr(lib, s).restype = C.c_int
     _lib = lib
     return lib

@@ -1,0 +1,27 @@
+"""The grid and depth-bin helpers of the reference's camera branch under its names (opencood/utils/camera_utils.py:129-135, 187-196):
+what ``LiftSplatShoot.__init__`` and ``create_frustum`` call.  Results are bit-equal to the reference's (tests/golden/lift_splat.npz)."""
+import numpy as np
+import torch
+
+
+def gen_dx_bx(xbound, ybound, zbound):
+    """``[low, high, step]`` per axis -> (dx f32 [3] cell size, bx f32 [3] centre of the first cell, nx i64 [3] cells).  The Python
+    doubles are rounded to float32 once; the cell count is the double quotient truncated toward zero, as ``torch.LongTensor`` does."""
+    bounds = (xbound, ybound, zbound)
+    dx = torch.tensor([float(b[2]) for b in bounds], dtype=torch.float32)
+    bx = torch.tensor([b[0] + b[2] / 2.0 for b in bounds], dtype=torch.float32)
+    nx = torch.tensor([int((b[1] - b[0]) / b[2]) for b in bounds], dtype=torch.int64)
+    return dx, bx, nx
+
+
+def depth_discretization(depth_min, depth_max, num_bins, mode):
+    """The lower edges of ``num_bins`` depth bins, float64 [num_bins]: ``UD`` uniform, ``LID`` linearly increasing bin sizes
+    (https://arxiv.org/abs/2005.13423)."""
+    k = np.arange(num_bins)
+    if mode == "UD":
+        bin_size = (depth_max - depth_min) / num_bins
+        return depth_min + bin_size * k
+    if mode == "LID":
+        bin_size = 2 * (depth_max - depth_min) / (num_bins * (1 + num_bins))
+        return depth_min + bin_size * (k * np.arange(1, 1 + num_bins)) / 2
+    raise NotImplementedError(f"depth discretization mode {mode!r}: 'UD' or 'LID'")
