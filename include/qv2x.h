@@ -503,7 +503,9 @@ int qv2x_codebook_encode_f32in(const qv2x_encode_desc* desc /* host */, const fl
  * (warp_affine_simple, as qv2x_fuse_att_f32), warped scores that are exactly 0 masked to -inf, softmax over the agents (NaN -> 0),
  * score-weighted sum of the warped features.  The descriptor's agents / h / w / max_cav / ego / metres fields are used.
  *   feats f32 [agents][h*w][channels] (channels last), score f32 [agents][h*w] (sigmoid(occupancy) + 1e-4, camera crop mask applied),
- *   pairwise f64 [max_cav][max_cav][4][4];  out f32 [h*w][channels]. */
+ *   pairwise f64 [max_cav][max_cav][4][4];  out f32 [h*w][channels].
+ *   channels: any multiple of 64 (64, 128, 192, ...), for this entry, _f32p and _i8 alike; 1 <= agents <= 8, agents <= max_cav,
+ *   0 <= ego < agents. */
 int qv2x_pyramid_weighted_fuse_f32(const qv2x_fuse_desc* desc /* host */, int channels, const float* feats, const float* score,
                                    const double* pairwise, float* out, void* stream);
 

@@ -118,11 +118,11 @@ def pairwise_from_poses(poses, max_cav):
 
 # ---- HEAL Pyramid fusion, one scale ----------------------------------------------------------------
 
-def weighted_fuse(x, score, affine_b, n):
+def weighted_fuse(x, score, affine_b, n, ego=0):
     """``pyramid_fuse.weighted_fuse`` (opencood/models/fuse_modules/pyramid_fuse.py:17-62) for one scene and one scale:
-    x [n, h, w, c], score [n, h, w, 1] -> [h, w, c].  Features and scores warped into agent 0's frame; warped scores equal to 0
-    masked to -inf; softmax over the agents with NaN (every agent masked) -> 0; score-weighted sum in agent order."""
-    theta = affine_b[:n, :n][0]
+    x [n, h, w, c], score [n, h, w, 1] -> [h, w, c].  Features and scores warped into agent ``ego``'s frame (the reference: agent 0);
+    warped scores equal to 0 masked to -inf; softmax over the agents with NaN (every agent masked) -> 0; score-weighted sum in agent order."""
+    theta = affine_b[ego, :n]
     grid = affine_grid(theta, x.shape[1], x.shape[2]).astype(np.float32)
     fx = grid_sample_bilinear_zeros(np.ascontiguousarray(x, dtype=np.float32), grid)
     sx = grid_sample_bilinear_zeros(np.ascontiguousarray(score, dtype=np.float32), grid)

@@ -6,7 +6,7 @@
 // A workgroup owns 16 consecutive ego cells and works in two phases.  (1) thread = cell (16 threads): the float64 -> fp32 sampling grid
 // of fuse_att.h, the four taps and their weights, the warped score and the softmax over the agents -- per-cell scalars, parked in LDS
 // (tap cells, tap weights, p per agent).  (2) lanes = channels, four per lane, every wave four of the cells: 4 / 2 / 1 cells per step
-// for 64 / 128 / >= 256 channels, the per-cell scalars read back as LDS broadcasts.  (The first version ran phase 1 on every lane of a
+// for 64 / 128 / any other multiple of 64 channels, the per-cell scalars read back as LDS broadcasts.  (The first version ran phase 1 on every lane of a
 // wave per cell: 73 us for the 100 x 352 x 64 level, against 4 us of traffic; 64 cells per wave starves the 25 x 88 level of waves.)
 // Agent order in the sums = agent index, as torch.sum(dim=0).
 #include "fuse_att.h"
@@ -75,7 +75,9 @@ __global__ __launch_bounds__(256) void pyramid_weighted_fuse_kernel(const PyrArg
     }
     __syncthreads();
     // ---- phase 2: four channels per lane; wave w takes cells 4 w .. 4 w + 3 ------------------------------------------------------------
-    const int lpc = min(a.c >> 2, 64);                   // lanes per cell (16, 32, 64)
+    // lanes per cell: 16 / 32 for 64 / 128 channels, a whole wave for everything else (lpc must divide 64: at 192 channels c >> 2 = 48
+    // would put lanes 48..63 on cell ci + 1, past rec[] in wave 3; with 64 the `ch >= a.c` test below idles them instead)
+    const int lpc = a.c == 64 ? 16 : a.c == 128 ? 32 : 64;
     const int cps = 64 / lpc;                            // cells per step
     const int sub = lane / lpc, l4 = (lane - sub * lpc) * 4;
     for (int step = 0; step < 4 / cps; ++step) {

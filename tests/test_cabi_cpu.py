@@ -259,6 +259,96 @@ def test_argument_errors_of_the_pyramid_entries_without_gpu():
     assert l.qv2x_postprocess_late_workspace_bytes(C.byref(pp), 9) == -1 and l.qv2x_postprocess_late_workspace_bytes(C.byref(pp), 2) > 0
 
 
+def test_argument_errors_of_the_fp32_path_and_weighted_fuse_entries_without_gpu():
+    """csrc/fp32_path.hip, qv2x_codebook_decode_f32 and the weighted-fuse entries refuse bad descriptors / pointers on the host, before any
+    launch: the return code and, where the message names the reason, a word of it"""
+    from quantv2x_amd import lib
+    l = _lib()
+    buf = np.zeros(4096 + 64, np.uint8)
+    base = (buf.ctypes.data + 63) & ~63
+    p, odd = C.c_void_p(base), C.c_void_p(base + 4)
+    err = l.qv2x_last_error
+
+    def desc(**kw):
+        d = lib.F32ConvDesc()
+        d.n, d.h, d.w, d.cin_total, d.cin0, d.cin, d.stride, d.cout, d.out_ctotal, d.out_c0, d.relu = 1, 4, 4, 16, 0, 16, 1, 64, 64, 0, 1
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return C.byref(d)
+
+    for fn in (l.qv2x_conv3x3_f32, l.qv2x_deconv_f32):
+        assert fn(desc(cin=12), p, p, p, p, None) == -2 and b"multiples of 8" in err()                # cin % 8
+        assert fn(desc(cin0=2, cin=8), p, p, p, p, None) == -2                                         # cin0 % 4
+        assert fn(desc(cin0=8, cin=8, cin_total=12), p, p, p, p, None) == -2 and b"window 8 + 8 of 12" in err()
+        assert fn(desc(cin0=12, cin=8), p, p, p, p, None) == -2                                        # window past cin_total
+        assert fn(desc(out_c0=8), p, p, p, p, None) == -2 and b"output channel window" in err()        # 8 + 64 > 64
+        assert fn(desc(out_c0=-4, out_ctotal=128), p, p, p, p, None) == -2
+        assert fn(desc(), odd, p, p, p, None) == -2 and b"16-byte aligned" in err()                    # in
+        assert fn(desc(), p, odd, p, p, None) == -2 and b"16-byte aligned" in err()                    # w
+        assert fn(desc(n=0), p, p, p, p, None) == -2
+        for args in ((None, p, p, p, p), (desc(), None, p, p, p), (desc(), p, None, p, p), (desc(), p, p, None, p), (desc(), p, p, p, None)):
+            assert fn(*args, None) == -1 and b"null" in err()
+    assert l.qv2x_conv3x3_f32(desc(stride=3), p, p, p, p, None) == -1 and b"stride 1 or 2" in err()
+    assert l.qv2x_conv3x3_f32(desc(stride=0), p, p, p, p, None) == -1
+    assert l.qv2x_conv3x3_f32(desc(cout=96, out_ctotal=96), p, p, p, p, None) == -2 and b"multiples of 64" in err()
+    for s in (0, 9):
+        assert l.qv2x_deconv_f32(desc(stride=s), p, p, p, p, None) == -1 and b"stride 1..8" in err()
+    assert l.qv2x_deconv_f32(desc(stride=2, cout=8), p, p, p, p, None) == -2 and b"multiples of 64" in err()       # 32 columns
+    assert l.qv2x_deconv_f32(desc(stride=3, cout=32, out_ctotal=32), p, p, p, p, None) == -2                        # 288 columns
+
+    fl = lambda k: (C.c_float * k)()
+    w, b, vox, off = fl(640), fl(64), fl(3), fl(3)
+    pfn = l.qv2x_pfn_scatter_f32
+    assert pfn(None, None, None, 0, 5, None, None, None, None, None, 1, 4, 4, None) == 0                # M = 0: nothing to do
+    assert pfn(None, p, p, 1, 5, w, b, vox, off, p, 1, 4, 4, None) == -1 and b"null" in err()
+    assert pfn(p, p, p, 1, 5, None, b, vox, off, p, 1, 4, 4, None) == -1 and b"null" in err()
+    assert pfn(p, p, p, 1, 5, w, b, vox, off, None, 1, 4, 4, None) == -1 and b"null" in err()
+    assert pfn(p, p, p, -1, 5, w, b, vox, off, p, 1, 4, 4, None) == -1 and b"bad sizes" in err()
+    assert pfn(p, p, p, 1, 0, w, b, vox, off, p, 1, 4, 4, None) == -1
+    assert pfn(p, p, p, 1, 5, w, b, vox, off, p, 0, 4, 4, None) == -1
+    assert pfn(p, p, p, 1, 5, w, b, vox, off, p, 1, 4, 0, None) == -1
+    assert pfn(odd, p, p, 1, 5, w, b, vox, off, p, 1, 4, 4, None) == -2 and b"aligned" in err()
+    assert pfn(p, odd, p, 1, 5, w, b, vox, off, p, 1, 4, 4, None) == -2
+
+    assert l.qv2x_add_relu_f32(p, p, p, 0, None) == -2 and l.qv2x_add_relu_f32(p, p, p, -4, None) == -2
+    assert l.qv2x_add_relu_f32(odd, p, p, 8, None) == -2 and l.qv2x_add_relu_f32(p, odd, p, 8, None) == -2 and l.qv2x_add_relu_f32(p, p, odd, 8, None) == -2
+    assert b"16-byte aligned" in err()
+    assert l.qv2x_add_relu_f32(None, p, p, 8, None) == -1 and l.qv2x_add_relu_f32(p, p, None, 8, None) == -1 and b"null" in err()
+    assert l.qv2x_occ_sigmoid_f32(None, 1, 4, 4, 64, p, p, None) == -1 and l.qv2x_occ_sigmoid_f32(p, 1, 4, 4, 64, p, None, None) == -1
+    assert l.qv2x_occ_sigmoid_f32(p, 0, 4, 4, 64, p, p, None) == -1 and l.qv2x_occ_sigmoid_f32(p, 1, 4, 4, 0, p, p, None) == -1 and b"bad shape" in err()
+
+    dec = l.qv2x_codebook_decode_f32
+    assert dec(p, 16, 16, 1, 16, 3, 128, 64, odd, p, p, None) == -2 and b"16-byte aligned" in err()     # lut
+    assert dec(p, 16, 16, 1, 16, 3, 128, 64, p, odd, p, None) == -2                                     # bias
+    assert dec(p, 16, 16, 1, 16, 3, 128, 64, p, p, odd, None) == -2                                     # out
+    assert dec(p, 16, 16, 1, 16, 3, 257, 64, p, p, p, None) == -1 and dec(p, 16, 16, 1, 16, 0, 128, 64, p, p, p, None) == -1
+    assert dec(p, 16, 16, 0, 16, 3, 128, 64, p, p, p, None) == -1 and b"bad sizes" in err()
+    assert dec(None, 16, 16, 1, 16, 3, 128, 64, p, p, p, None) == -1 and b"null" in err()
+
+    def fuse(**kw):
+        f = lib.FuseDesc()
+        f.agents, f.h, f.w, f.max_cav, f.ego, f.h_metres, f.w_metres, f.discrete_ratio = 2, 4, 4, 5, 0, 1.0, 2.0, 1.0
+        for k, v in kw.items():
+            setattr(f, k, v)
+        return C.byref(f)
+
+    for fn in (l.qv2x_pyramid_weighted_fuse_f32, l.qv2x_pyramid_weighted_fuse_f32p):
+        call = lambda d, ch=64: fn(d, ch, p, p, p, p, None)
+        for bad in (dict(agents=0), dict(agents=9, max_cav=9), dict(ego=-1), dict(ego=2), dict(agents=3, max_cav=2)):
+            assert call(fuse(**bad)) == -1 and b"agents" in err(), bad
+        for ch in (32, 96, 0, -64):
+            assert call(fuse(), ch) == -1 and b"channels" in err(), ch
+        for bad in (dict(h_metres=0.0), dict(w_metres=-1.0), dict(discrete_ratio=0.0), dict(h_metres=float("nan")), dict(w_metres=float("nan")),
+                    dict(discrete_ratio=float("nan"))):
+            assert call(fuse(**bad)) == -1 and b"extent" in err(), bad
+        assert call(fuse(h=0)) == -1 and call(fuse(w=0)) == -1
+        assert fn(None, 64, p, p, p, p, None) == -1 and fn(fuse(), 64, p, p, None, p, None) == -1 and b"null" in err()
+    i8 = l.qv2x_pyramid_weighted_fuse_i8
+    assert i8(fuse(), 96, p, 0, 0.1, p, p, p, None) == -1 and b"channels" in err()
+    assert i8(fuse(agents=9, max_cav=9), 64, p, 0, 0.1, p, p, p, None) == -1 and i8(fuse(ego=2), 64, p, 0, 0.1, p, p, p, None) == -1
+    assert i8(fuse(h_metres=float("nan")), 64, p, 0, 0.1, p, p, p, None) == -1 and b"extent" in err()
+
+
 def test_collapsed_encoder_algebra_matches_the_exact_checker():
     """engine.collapse_encoder (the operands of the OPT-IN qv2x_codebook_encode_collapsed_f32) evaluated in numpy: on the tiny scene every
     index equals the exact checker's, or differs only where the exact top-2 gap is within rounding error."""
