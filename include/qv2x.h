@@ -909,6 +909,59 @@ int qv2x_lss_plan_f32(const qv2x_lss_desc* desc /* host */, const float* frustum
 int qv2x_lss_splat_f32(const qv2x_lss_desc* desc /* host */, const float* depth, const float* feats, int mode, void* workspace, float* out,
                        void* stream);
 
+/* ---- camera agents: the two ends of the int8 ResNet image encoder (QuantCamEncode_Resnet101, opencood/quant/quant_block.py:744-860) ------
+ * Between them the trunk's bottlenecks run on qv2x_conv1x1_i8 / qv2x_conv3x3_i8.  quantv2x_amd/camera_encoder.py states both entries in
+ * numpy (stem_statement, cam_heads_statement); DESIGN.md section 14.
+ *
+ * STEM: f32 image -> 7x7 stride-2 pad-3 convolution (BN folded, weights dequantized on the host) -> ReLU -> activation quantizer ->
+ * 3x3 stride-2 pad-1 max-pool, one launch.
+ *   img      f32; view v, channel c < 3 starts at img + v * view_stride + c * h * w (floats), view_stride >= 3 * h * w: a 4-channel RGB-D
+ *            tensor passes with view_stride = 4 * h * w and its fourth channel is never read.
+ *   wdeq     f32 [7][7][3][64] = [ky][kx][ci][co], fl((code - zp[co]) * delta[co]);   bias f32 [64]
+ *   conv     Hc = (h - 1) / 2 + 1, Wc likewise.  Per channel co and conv pixel (i, j): acc = +0; for ky, kx, ci ascending
+ *            acc = fmaf(x[ci][2i + ky - 3][2j + kx - 3], wdeq[ky][kx][ci][co], acc), taps outside the image as x = 0 (the same bits as
+ *            skipping them: fmaf(0, w, acc) = acc for finite w, and acc is never -0);  y = acc + bias[co]
+ *   code     clamp(rint(fma(max(y, 0), fl(1 / out_delta), out_zp)), 0, 255)
+ *   pool     Hp = (Hc - 1) / 2 + 1, Wp likewise; out[p][q] = max of the codes at conv rows 2p - 1 .. 2p + 1, columns 2q - 1 .. 2q + 1 inside
+ *            Hc x Wc (torch's -inf padding; the quantizer is monotone, so the max of the codes is the code of the max)
+ *   out      padded i8 BEV [views][Hp + 2][Wp + 2][64] as code - 128; the interior is written, the ring keeps its bytes.
+ * QV2X_EINVAL: a null pointer; views, h, w < 1; views * Hc * Wc outside int32; view_stride < 3 * h * w; out_delta not > 0; out_zp outside
+ * 0..255.  QV2X_EALIGN: img not 4-byte, wdeq / bias / out not 16-byte aligned.  Non-finite pixels: undefined codes where they reach. */
+typedef struct {
+    int32_t views;           /* images: samples * cameras */
+    int32_t h, w;            /* image rows, columns */
+    int32_t reserved;        /* 0 */
+    int64_t view_stride;     /* floats between consecutive views */
+    float out_delta, out_zp; /* the stem's activation quantizer */
+} qv2x_cam_stem_desc;
+int qv2x_cam_stem_f32(const qv2x_cam_stem_desc* desc /* host */, const float* img, const float* wdeq, const float* bias, int8_t* out,
+                      void* stream);
+
+/* HEADS: the 1x1 depth head (cin -> depth_bins) and image head (cin -> features) on the trunk's codes, both in one launch, each followed
+ * by its own activation quantizer WITHOUT a ReLU (zero point anywhere in 0..255) and dequantized: the two f32 tensors the splat reads.
+ *   in       padded i8 BEV [views][h + 2][w + 2][cin], code - 128, input zero point folded into corr (below)
+ *   rows     the output rows of both heads in one list: depth_bins rows padded to Dp = the next multiple of 32, then features rows padded
+ *            to a multiple of 32; R = their sum.  Padding rows hold zeros in every array and are never stored.
+ *   w_frag   i8 [R / 32][cin / 32][2][32][16], weight code - 128: the A fragments of v_mfma_i32_32x32x32_i8 as qv2x_conv1x1_i8 takes them
+ *   scale    f32 [R] = fl(in_delta * w_delta[co]);  aw i32 [R] = 128 - w_zp[co];  corr i32 [R] = ax * sum_ci (w - 128) + cin * ax * aw with
+ *            ax = 128 - in_zp;  bias f32 [R]
+ *   T        sum_ci (x - in_zp) * (w - w_zp[co]), exact in int32;   y = bias[co] + float(T) * scale[co]  (one rounded product, one rounded add)
+ *   code     clamp(rint(fma(y, fl(1 / delta), zp)), 0, 255) with the head's own (delta, zp);   value = fl(float(code - zp) * delta)
+ *   depth    f32 [views][depth_bins][h][w];   feats f32 [views][features][h][w]: what qv2x_lss_splat_f32 takes, no transpose between.
+ * QV2X_EINVAL: a null pointer; views, h, w < 1; views * h * w outside int32; depth_bins outside 1..256; features outside 4..256; a delta not
+ * > 0 or a zero point outside 0..255.  QV2X_EALIGN: cin % 32 != 0 or outside 32..4096; features % 4 != 0; in, w_frag, scale, corr, aw, bias
+ * not 16-byte, depth / feats not 4-byte aligned. */
+typedef struct {
+    int32_t views;                   /* maps: samples * cameras */
+    int32_t h, w;                    /* feature map */
+    int32_t cin;                     /* input channels, % 32 == 0 */
+    int32_t depth_bins, features;    /* D in 1..256; C % 4 == 0 in 4..256 */
+    float depth_delta, depth_zp;     /* depth head's activation quantizer */
+    float feat_delta, feat_zp;       /* image head's */
+} qv2x_cam_heads_desc;
+int qv2x_cam_heads_i8(const qv2x_cam_heads_desc* desc /* host */, const int8_t* in, const int8_t* w_frag, const float* scale,
+                      const int32_t* corr, const int32_t* aw, const float* bias, float* depth, float* feats, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

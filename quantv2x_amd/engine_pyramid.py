@@ -138,6 +138,59 @@ class _Block:
         self.in_q, self.out_q = in_q, _q(state, name)
 
 
+def launch_conv3x3(lib, layer: _ConvLayer, x, n, h, w, out, out_q, res_mode=0, res=None, res_q=(0.0, 128)):
+    """One 3x3 QuantModule convolution on codes (``qv2x_conv3x3_i8``, its wide form where the shape allows it, or ``_res`` with a fused
+    residual end).  Shared by the Pyramid engine and the camera encoder."""
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.cin_total, d.stride, d.cout = n, h, w, x.shape[-1], layer.stride, layer.cout
+    d.ngroups = len(layer.groups)
+    for i, (c0, c, zx) in enumerate(layer.groups):
+        d.group_c0[i], d.group_c[i], d.group_zx[i] = c0, c, zx
+    d.out_ctotal, d.out_c0, d.relu = out.shape[-1], 0, 1
+    d.out_delta, d.out_zp = out_q[0], float(out_q[1])
+    st = L.current_stream()
+    if res_mode:
+        L.check(lib.qv2x_conv3x3_i8_res(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
+                                        L.ptr(layer.bias), res_mode, L.ptr(res), int(res_q[1]), float(res_q[0]), L.ptr(out), st), layer.name)
+        return
+    if lib.qv2x_conv3x3_i8_wide_ok(C.byref(d)):
+        if layer.w_wide is None:
+            layer.w_wide = torch.empty_like(layer.w)
+            L.check(lib.qv2x_conv3x3_i8_pack_wide(C.byref(d), L.ptr(layer.w), L.ptr(layer.w_wide), st), layer.name)
+        L.check(lib.qv2x_conv3x3_i8_wide(C.byref(d), L.ptr(x), L.ptr(layer.w_wide), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
+                                         L.ptr(layer.bias), L.ptr(out), st), layer.name)
+        return
+    L.check(lib.qv2x_conv3x3_i8(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
+                                L.ptr(layer.bias), L.ptr(out), st), layer.name)
+
+
+def launch_conv1x1(lib, layer: _Conv1x1, x, n, h, w, out, mode, out_q=None, res=None, res_q=(0.0, 128)):
+    """One 1x1 QuantModule convolution on codes (``qv2x_conv1x1_i8``): mode 0 codes out, 1 the fp32 map, 2 / 3 the fused end of a residual
+    block with an fp32 / a code shortcut."""
+    d = L.Conv1x1Desc()
+    d.n, d.h, d.w, d.cin, d.cout, d.stride = n, h, w, layer.cin, layer.cout, layer.stride
+    d.mode, d.relu = mode, 1
+    if mode != 1:
+        d.out_ctotal, d.out_c0 = out.shape[-1], 0
+        d.out_delta, d.out_zp = out_q[0], float(out_q[1])
+    d.res_zx, d.res_delta = int(res_q[1]), float(res_q[0])
+    L.check(lib.qv2x_conv1x1_i8(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw), L.ptr(layer.bias),
+                                L.ptr(res), L.ptr(out), L.current_stream()), layer.name)
+
+
+def bottleneck_layers(lib, blk, conv2, x, xq, n, h, w, ho, wo, t1, t2, ds, out):
+    """The per-layer path of a QuantBottleneck on codes ``x`` (quantizer ``xq``) at (h, w): conv1 -> ``t1``, ``conv2(layer, t1, n, h, w, t2)``
+    (the grouped 3x3 of the Pyramid levels, the dense one of the camera trunk; it carries the block's stride) -> ``t2`` at (ho, wo), then conv3
+    with the end of the block in its epilogue: + the strided 1x1 shortcut (fp32 rows in ``ds``) or + the dequantized input codes."""
+    launch_conv1x1(lib, blk.conv1, x, n, h, w, t1, 0, blk.conv1.out_q)
+    conv2(blk.conv2, t1, n, h, w, t2)
+    if blk.down is not None:
+        launch_conv1x1(lib, blk.down, x, n, h, w, ds, 1)
+        launch_conv1x1(lib, blk.conv3, t2, n, ho, wo, out, 2, blk.out_q, ds)
+    else:
+        launch_conv1x1(lib, blk.conv3, t2, n, ho, wo, out, 3, blk.out_q, x, xq)
+
+
 class DeployedPyramidModel(nn.Module):
     """Same call contract as the reference's model: ``out = model(data_dict)`` (the hard ``encode -> decode`` path of
     ``forward_with_encdec``), plus ``encode_features`` / ``decode_features`` as the reference's encdec class exposes them."""
@@ -329,38 +382,10 @@ class DeployedPyramidModel(nn.Module):
 
     # ---- launch helpers ------------------------------------------------------------------------------------------------------------
     def _conv3x3(self, layer: _ConvLayer, x, n, h, w, out, out_q, res_mode=0, res=None, res_q=(0.0, 128)):
-        d = L.ConvDesc()
-        d.n, d.h, d.w, d.cin_total, d.stride, d.cout = n, h, w, x.shape[-1], layer.stride, layer.cout
-        d.ngroups = len(layer.groups)
-        for i, (c0, c, zx) in enumerate(layer.groups):
-            d.group_c0[i], d.group_c[i], d.group_zx[i] = c0, c, zx
-        d.out_ctotal, d.out_c0, d.relu = out.shape[-1], 0, 1
-        d.out_delta, d.out_zp = out_q[0], float(out_q[1])
-        st = L.current_stream()
-        if res_mode:
-            L.check(self.lib.qv2x_conv3x3_i8_res(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
-                                                 L.ptr(layer.bias), res_mode, L.ptr(res), int(res_q[1]), float(res_q[0]), L.ptr(out), st), layer.name)
-            return
-        if self.lib.qv2x_conv3x3_i8_wide_ok(C.byref(d)):
-            if layer.w_wide is None:
-                layer.w_wide = torch.empty_like(layer.w)
-                L.check(self.lib.qv2x_conv3x3_i8_pack_wide(C.byref(d), L.ptr(layer.w), L.ptr(layer.w_wide), st), layer.name)
-            L.check(self.lib.qv2x_conv3x3_i8_wide(C.byref(d), L.ptr(x), L.ptr(layer.w_wide), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
-                                                  L.ptr(layer.bias), L.ptr(out), st), layer.name)
-            return
-        L.check(self.lib.qv2x_conv3x3_i8(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
-                                         L.ptr(layer.bias), L.ptr(out), st), layer.name)
+        launch_conv3x3(self.lib, layer, x, n, h, w, out, out_q, res_mode, res, res_q)
 
     def _conv1x1(self, layer: _Conv1x1, x, n, h, w, out, mode, out_q=None, res=None, res_q=(0.0, 128)):
-        d = L.Conv1x1Desc()
-        d.n, d.h, d.w, d.cin, d.cout, d.stride = n, h, w, layer.cin, layer.cout, layer.stride
-        d.mode, d.relu = mode, 1
-        if mode != 1:
-            d.out_ctotal, d.out_c0 = out.shape[-1], 0
-            d.out_delta, d.out_zp = out_q[0], float(out_q[1])
-        d.res_zx, d.res_delta = int(res_q[1]), float(res_q[0])
-        L.check(self.lib.qv2x_conv1x1_i8(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw), L.ptr(layer.bias),
-                                         L.ptr(res), L.ptr(out), L.current_stream()), layer.name)
+        launch_conv1x1(self.lib, layer, x, n, h, w, out, mode, out_q, res, res_q)
 
     def _gconv(self, layer: _GConv, x, n, h, w, out):
         d = L.GconvDesc()
@@ -455,18 +480,12 @@ class DeployedPyramidModel(nn.Module):
         if self.fuse_blocks and blk.stride == 1 and blk.down is None and not blk.f32_input and blk.cout in self.fuse_planes and blk.conv2.c == 2 * blk.cout:
             return self._bottleneck(blk, x, xq, n, h, w, out)
         t1 = lv["t1_in"] if (h, w) != (ho, wo) else lv["t1"]
-        if blk.f32_input:
-            self._dense_f32in(blk.conv1, feats_f32, n, h, w, t1)
-        else:
-            self._conv1x1(blk.conv1, x, n, h, w, t1, 0, blk.conv1.out_q)
+        if not blk.f32_input:
+            return bottleneck_layers(self.lib, blk, self._gconv, x, xq, n, h, w, ho, wo, t1, lv["t2"], lv["ds"], out)
+        # the first block behind the codebook: its input is the decoded fp32 feature (never with a 1x1 shortcut: _Block refuses that)
+        self._dense_f32in(blk.conv1, feats_f32, n, h, w, t1)
         self._gconv(blk.conv2, t1, n, h, w, lv["t2"])
-        if blk.down is not None:
-            self._conv1x1(blk.down, x, n, h, w, lv["ds"], 1)
-            self._conv1x1(blk.conv3, lv["t2"], n, ho, wo, out, 2, blk.out_q, lv["ds"])
-        elif blk.f32_input:
-            self._conv1x1(blk.conv3, lv["t2"], n, ho, wo, out, 2, blk.out_q, feats_f32)
-        else:
-            self._conv1x1(blk.conv3, lv["t2"], n, ho, wo, out, 3, blk.out_q, x, xq)
+        self._conv1x1(blk.conv3, lv["t2"], n, ho, wo, out, 2, blk.out_q, feats_f32)
 
     def _fuse_level(self, lvl, lv, x, xq, n, h, w, lens, pairwise, ego, cat, c0):
         """occupancy head + score, weighted_fuse of every scene, the level's deblock into the concat; returns the fp32 occupancy maps"""

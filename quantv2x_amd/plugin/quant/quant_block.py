@@ -2,7 +2,7 @@
 ``opencood/quant/quant_block.py``: ``BaseQuantBlock :45-65``, ``QuantBaseBEVBackbone :243-335``,
 ``QuantDoubleConv / QuantDownsampleConv :552-586``, ``QuantPFNLayer :589-629`` (extra activation
 quantizer after the ReLU, before the max), ``QuantPillarVFE :632-715``, ``QuantPointPillar :718-741``,
-``QuantNaiveCompressor :1543-1570``; the Pyramid model's blocks ``QuantBasicBlock :68-97``, ``QuantBottleneck :100-131``,
+``QuantNaiveCompressor :1543-1570``, the camera branch ``QuantCamEncode_Resnet101 :745-851`` and ``QuantLiftSplatShoot :854-985``; the Pyramid model's blocks ``QuantBasicBlock :68-97``, ``QuantBottleneck :100-131``,
 ``QuantResNetModified :338-395``, ``QuantResNetBEVBackbone :398-459``, ``QuantPyramidFusion :462-549``; registries ``opencood_specials :1581-1591``,
 ``specials_unquantized_names :1599-1615``.
 """
@@ -11,11 +11,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..models.fuse_modules.pyramid_fuse import PyramidFusion, weighted_fuse
-from ..models.heter_encoders import SECOND, PointPillar
+from ..models.heter_encoders import SECOND, LiftSplatShoot, PointPillar, pool_bev
 from ..models.sub_modules.base_bev_backbone import BaseBEVBackbone
 from ..models.sub_modules.base_bev_backbone_resnet import ResNetBEVBackbone
 from ..models.sub_modules.resblock import BasicBlock, Bottleneck, ResNetModified
 from ..models.sub_modules.downsample_conv import DoubleConv, DownsampleConv
+from ..models.sub_modules.lss_submodule import CamEncode_Resnet101, features_and_depth, gt_depth_dist, lift
 from ..models.sub_modules.naive_compress import NaiveCompressor
 from ..models.sub_modules.pillar_vfe import PFNLayer, PillarVFE
 from ..models.sub_modules.sparse_backbone_3d import VoxelBackBone8x
@@ -380,6 +381,75 @@ class QuantPyramidFusion(QuantResNetBEVBackbone):
         return self.forward_collab(spatial_features, record_len, affine_matrix, agent_modality_list, cam_crop_info)
 
 
+class QuantCamEncode_Resnet101(BaseQuantBlock):
+    """``CamEncode_Resnet101`` under PTQ: ``conv1`` with ``bn1`` / ReLU attached and its own activation quantizer in front of the max-pool,
+    a ``QuantBottleneck`` per trunk block, and the two 1x1 heads as plain ``QuantModule``s (no ReLU: two-sided quantizers)."""
+
+    def __init__(self, camencode: CamEncode_Resnet101, weight_quant_params: dict = {}, act_quant_params: dict = {}):
+        super().__init__()
+        for k in ("D", "C", "downsample", "d_min", "d_max", "num_bins", "mode", "use_gt_depth", "depth_supervision"):
+            setattr(self, k, getattr(camencode, k))
+        self.conv1 = QuantModule(camencode.conv1, weight_quant_params, act_quant_params)
+        self.conv1.norm_function = camencode.bn1
+        self.conv1.activation_function = camencode.relu
+        self.maxpool = camencode.maxpool
+        wrap = lambda blk: (QuantBasicBlock if isinstance(blk, BasicBlock) else QuantBottleneck)(blk, weight_quant_params, act_quant_params)
+        self.layer1 = nn.Sequential(*[wrap(b) for b in camencode.layer1])
+        self.layer2 = nn.Sequential(*[wrap(b) for b in camencode.layer2])
+        if not self.use_gt_depth:
+            self.depth_head = QuantModule(camencode.depth_head, weight_quant_params, act_quant_params)
+        self.image_head = QuantModule(camencode.image_head, weight_quant_params, act_quant_params)
+
+    def get_depth_dist(self, x, eps=1e-5):
+        return F.softmax(x, dim=1)
+
+    def get_gt_depth_dist(self, x):
+        return gt_depth_dist(self, x)
+
+    def resnet101_forward(self, x):
+        return self.layer2(self.layer1(self.maxpool(self.conv1(x))))         # bn1 and the ReLU run inside conv1
+
+    def get_resnet_features(self, x):
+        return self.resnet101_forward(x)
+
+    def forward(self, x):
+        return lift(self, x)
+
+
+class QuantLiftSplatShoot(nn.Module):
+    def __init__(self, lift_splat_shoot: LiftSplatShoot, weight_quant_params: dict = {}, act_quant_params: dict = {}):
+        super().__init__()
+        src = lift_splat_shoot
+        for k in ("grid_conf", "data_aug_conf", "depth_supervision", "downsample", "camC", "use_quickcumsum", "D", "camera_encoder_type"):
+            setattr(self, k, getattr(src, k))
+        for k in ("dx", "bx", "nx", "frustum"):
+            self.register_buffer(k, getattr(src, k), persistent=False)
+        if self.camera_encoder_type == 'EfficientNet':
+            raise NotImplementedError("EfficientNet is not supported in QuantLiftSplatShoot yet.")
+        elif self.camera_encoder_type == 'Resnet101':
+            self.camencode = QuantCamEncode_Resnet101(src.camencode, weight_quant_params, act_quant_params)
+        self._stages = {}
+
+    def get_cam_feats(self, x):
+        b, n, c, h, w = x.shape
+        items, depth, mode, feats = features_and_depth(self.camencode, x.view(b * n, c, h, w))
+        want = (h // self.downsample, w // self.downsample)
+        if tuple(feats.shape[-2:]) != want:
+            raise ValueError(f"images of {h} x {w} leave the encoder as {tuple(feats.shape[-2:])}, not (H // downsample, W // downsample) = {want}")
+        return items, depth, mode, feats
+
+    def get_voxels(self, x, rots, trans, intrins, post_rots, post_trans):
+        items, depth, mode, feats = self.get_cam_feats(x)
+        return pool_bev(self, x.shape[0], x.shape[1], depth, mode, feats, rots, trans, intrins, post_rots, post_trans), items
+
+    def forward(self, data_dict, modality_name):
+        src = data_dict[f'inputs_{modality_name}']
+        x, items = self.get_voxels(*(src[k] for k in ('imgs', 'rots', 'trans', 'intrins', 'post_rots', 'post_trans')))
+        if self.depth_supervision:
+            self.depth_items = items
+        return x
+
+
 specials = {BasicBlock: QuantBasicBlock, Bottleneck: QuantBottleneck}
 
 opencood_specials = {
@@ -390,6 +460,7 @@ opencood_specials = {
     PointPillar: QuantPointPillar,
     SECOND: QuantSECOND,
     NaiveCompressor: QuantNaiveCompressor,
+    LiftSplatShoot: QuantLiftSplatShoot,
 }
 
 specials_unquantized = []

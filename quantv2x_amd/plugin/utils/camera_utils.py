@@ -1,5 +1,8 @@
 """The grid and depth-bin helpers of the reference's camera branch under its names (opencood/utils/camera_utils.py:129-135, 187-196):
-what ``LiftSplatShoot.__init__`` and ``create_frustum`` call.  Results are bit-equal to the reference's (tests/golden/lift_splat.npz)."""
+what ``LiftSplatShoot.__init__`` and ``create_frustum`` call, and ``bin_depths`` (:137-185) of the ground-truth depth path.  Results are bit-equal to
+the reference's (tests/golden/lift_splat.npz, tests/golden/cam_encode.npz)."""
+import math
+
 import numpy as np
 import torch
 
@@ -25,3 +28,26 @@ def depth_discretization(depth_min, depth_max, num_bins, mode):
         bin_size = 2 * (depth_max - depth_min) / (num_bins * (1 + num_bins))
         return depth_min + bin_size * (k * np.arange(1, 1 + num_bins)) / 2
     raise NotImplementedError(f"depth discretization mode {mode!r}: 'UD' or 'LID'")
+
+
+def bin_depths(depth_map, mode, depth_min, depth_max, num_bins, target=True):
+    """Metric depth -> depth-bin index, int64, the inverse of ``depth_discretization`` (plus ``SID``, log-spaced bins; reference
+    camera_utils.py:137-185).  The fractional index is clamped into ``[0, num_bins - 1]``, NaN and +inf landing in the last bin and -inf in
+    the first.  ``target=True`` (training targets) returns ``(indices, None)``; ``target=False`` also returns the mask of the depths that
+    lay INSIDE the range before the clamp, which ``get_gt_depth_dist`` multiplies onto the one-hot."""
+    if mode == "UD":
+        step = (depth_max - depth_min) / num_bins
+        frac = (depth_map - depth_min) / step
+    elif mode == "LID":
+        step = 2 * (depth_max - depth_min) / (num_bins * (1 + num_bins))
+        frac = -0.5 + 0.5 * torch.sqrt(1 + 8 * (depth_map - depth_min) / step)
+    elif mode == "SID":
+        frac = num_bins * (torch.log(1 + depth_map) - math.log(1 + depth_min)) / (math.log(1 + depth_max) - math.log(1 + depth_min))
+    else:
+        raise NotImplementedError(f"depth discretization mode {mode!r}: 'UD', 'LID' or 'SID'")
+    outside = (frac < 0) | (frac >= num_bins) | ~torch.isfinite(frac)
+    last = torch.full_like(frac, num_bins - 1)
+    frac = torch.where(frac < 0, torch.zeros_like(frac), frac)
+    frac = torch.where(frac >= num_bins, last, frac)
+    frac = torch.where(torch.isfinite(frac), frac, last)
+    return frac.type(torch.int64), (None if target else ~outside)

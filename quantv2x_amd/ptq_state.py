@@ -111,6 +111,31 @@ def _check_structure(model) -> None:
 _PER_MODALITY = re.compile(r"^(encoder|backbone|shrinker|aligner)_(m\d+)(\.|$)")
 
 
+def _module_entries(name: str, m) -> Dict[str, np.ndarray]:
+    """The ``<name>/...`` entries of one frozen ``QuantModule``."""
+    # W4A8 and the other sub-8-bit WEIGHT widths of the reference's PTQ script (scripts/inference/inference_quant.sh: --n_bits_w 4
+    # --n_bits_a 8; quant_layer.py:337-340 bitwidth_refactor, quant_model.py:115-127 set_first_last_layer_to_8bit) deploy unchanged:
+    # a b-bit code and its zero point lie in [0, 2^b - 1], stay uint8 and run on the same int8 kernels.  Activations stay 8-bit:
+    # the requantizing epilogues clamp to [0, 255].
+    if not 2 <= int(m.weight_quantizer.n_bits) <= 8:
+        raise ValueError(f"{name}: weight bit width {m.weight_quantizer.n_bits} (2..8 deploy)")
+    if m.act_quantizer.n_bits != 8:
+        raise NotImplementedError(f"{name}: {m.act_quantizer.n_bits}-bit activations -- the deployed path is WxA8 (every epilogue clamps codes to [0, 255])")
+    # AdaRoundQuantizer (adaptive_rounding.py:6-21) has no `inited`: it is built from an initialised quantizer
+    if not (getattr(m.weight_quantizer, "inited", True) and m.act_quantizer.inited):
+        raise ValueError(f"{name}: quantizers must be frozen (set_inited(True)) before export")
+    wq, aq = m.weight_quantizer, m.act_quantizer
+    return {
+        name + "/w_code": weight_codes(m),
+        name + "/w_delta": _np(torch.as_tensor(wq.delta)).reshape(-1).astype(np.float32),
+        name + "/w_zp": _np(torch.as_tensor(wq.zero_point)).reshape(-1).astype(np.float32),
+        name + "/bias": _np(m.bias).astype(np.float32) if m.bias is not None else np.zeros(0, np.float32),
+        name + "/a_delta": np.float32(_np(torch.as_tensor(aq.delta)).reshape(-1)[0]),
+        name + "/a_zp": np.float32(_np(torch.as_tensor(aq.zero_point)).reshape(-1)[0]),
+        name + "/a_off": np.bool_(bool(m.disable_act_quant)),
+    }
+
+
 def export_ptq_state(qt_model, modality: str = "m1") -> Dict[str, np.ndarray]:
     """``modality``: which of a heterogeneous model's per-modality stacks (``encoder_<m>`` / ``backbone_<m>`` / ``shrinker_<m>``,
     heter_model_baseline.py:41-75) this state carries, next to the shared codebook / fusion / heads.  Its keys are written under the
@@ -133,28 +158,9 @@ def export_ptq_state(qt_model, modality: str = "m1") -> Dict[str, np.ndarray]:
         if pm and pm.group(2) != modality:
             continue                                                # another modality's stack: in that modality's own state
         name = _PER_MODALITY.sub(lambda g: f"{g.group(1)}_m1{g.group(3)}", src_name) if pm else src_name
-        # W4A8 and the other sub-8-bit WEIGHT widths of the reference's PTQ script (scripts/inference/inference_quant.sh: --n_bits_w 4
-        # --n_bits_a 8; quant_layer.py:337-340 bitwidth_refactor, quant_model.py:115-127 set_first_last_layer_to_8bit) deploy unchanged:
-        # a b-bit code and its zero point lie in [0, 2^b - 1], stay uint8 and run on the same int8 kernels.  Activations stay 8-bit:
-        # the requantizing epilogues clamp to [0, 255].
-        if not 2 <= int(m.weight_quantizer.n_bits) <= 8:
-            raise ValueError(f"{name}: weight bit width {m.weight_quantizer.n_bits} (2..8 deploy)")
-        if m.act_quantizer.n_bits != 8:
-            raise NotImplementedError(f"{name}: {m.act_quantizer.n_bits}-bit activations -- the deployed path is WxA8 (every epilogue clamps codes to [0, 255])")
-        # AdaRoundQuantizer (adaptive_rounding.py:6-21) has no `inited`: it is built from an initialised quantizer
-        if not (getattr(m.weight_quantizer, "inited", True) and m.act_quantizer.inited):
-            raise ValueError(f"{name}: quantizers must be frozen (set_inited(True)) before export")
+        out.update(_module_entries(name, m))
         names.append(name)
         src_of[name] = src_name
-        wq, aq = m.weight_quantizer, m.act_quantizer
-        out[name + "/w_code"] = weight_codes(m)
-        out[name + "/w_delta"] = _np(torch.as_tensor(wq.delta)).reshape(-1).astype(np.float32)
-        out[name + "/w_zp"] = _np(torch.as_tensor(wq.zero_point)).reshape(-1).astype(np.float32)
-        out[name + "/bias"] = _np(m.bias).astype(np.float32) if m.bias is not None \
-            else np.zeros(0, np.float32)
-        out[name + "/a_delta"] = np.float32(_np(torch.as_tensor(aq.delta)).reshape(-1)[0])
-        out[name + "/a_zp"] = np.float32(_np(torch.as_tensor(aq.zero_point)).reshape(-1)[0])
-        out[name + "/a_off"] = np.bool_(bool(m.disable_act_quant))
     out["meta/module_names"] = np.array(names)
     out["meta/w_bits"] = np.array([int(modules[src_of[n]].weight_quantizer.n_bits) for n in names], dtype=np.int32)   # 8, or 2..7 (W4A8)
 
@@ -326,3 +332,52 @@ def export_second_state(enc) -> Dict[str, np.ndarray]:
     out["second/sparse_shape"] = np.asarray(enc.spconv_block.sparse_shape, dtype=np.int64)      # (D, H, W) of the input volume
     out["second/names"] = np.array([n for n, _ in layers])
     return out
+
+
+CAMERA_TRUNK = (("layer1", 3), ("layer2", 4))          # what CamEncode_Resnet101 keeps of torchvision's ResNet-101: layer1 and layer2
+
+
+def export_camera_state(lss) -> Dict[str, np.ndarray]:
+    """Frozen W8A8 state of a calibrated ``QuantLiftSplatShoot`` over ``QuantCamEncode_Resnet101`` (reference ``quant_block.py:744-985``):
+    the encoder's ``QuantModule``s under their own names (``conv1``, ``layer1.0.conv1`` ... ``layer2.3.conv3``, ``layerN.0.downsample``,
+    ``depth_head``, ``image_head``), the block quantizers (``layerN.M/a_delta, a_zp``) and under ``meta/`` what the lift-splat stage is built
+    from.  Only attribute names are used, so the reference's own objects export as the mirror's do."""
+    if "Voxel" in type(lss).__name__:
+        raise NotImplementedError("export_camera_state: LiftSplatShootVoxel keeps the height axis; the deployed path collapses it as LiftSplatShoot does")
+    kind = getattr(lss, "camera_encoder_type", None)
+    if kind != "Resnet101":
+        raise NotImplementedError(f"export_camera_state: camera_encoder {kind!r}; only 'Resnet101' has a quantized form (QuantLiftSplatShoot refuses "
+                                  "EfficientNet, quant_block.py:869-870)")
+    enc = lss.camencode
+    out: Dict[str, np.ndarray] = {}
+    names, blocks = [], []
+    for name, m in enc.named_modules():
+        if _is_quant_module(m):
+            if isinstance(getattr(m, "norm_function", None), torch.nn.modules.batchnorm._BatchNorm):
+                raise ValueError(f"{name}: its BatchNorm is not folded into the convolution (fold_bn.search_fold_and_remove_bn runs before "
+                                 "the model is wrapped); the deployed layers carry the folded weight and bias only")
+            out.update(_module_entries(name, m))
+            names.append(name)
+        elif type(m).__name__ == "QuantBottleneck":
+            if not m.act_quantizer.inited:
+                raise ValueError(f"{name}: quantizers must be frozen (set_inited(True)) before export")
+            out[name + "/a_delta"] = np.float32(_np(torch.as_tensor(m.act_quantizer.delta)).reshape(-1)[0])
+            out[name + "/a_zp"] = np.float32(_np(torch.as_tensor(m.act_quantizer.zero_point)).reshape(-1)[0])
+            out[name + "/a_off"] = np.bool_(not bool(m.use_act_quant))
+            blocks.append(name)
+        elif type(m).__name__ == "QuantBasicBlock":
+            raise NotImplementedError(f"{name}: the deployed camera trunk is made of bottlenecks (ResNet-101)")
+    want = [f"{layer}.{i}" for layer, n in CAMERA_TRUNK for i in range(n)]
+    if blocks != want:
+        raise NotImplementedError(f"export_camera_state: trunk blocks {blocks}; {want} expected (layer1 and layer2 of ResNet-101)")
+    out["meta/module_names"], out["meta/block_names"] = np.array(names), np.array(blocks)
+    out["meta/camera_encoder"] = np.array(kind)
+    out["meta/use_gt_depth"] = np.bool_(bool(enc.use_gt_depth))
+    out["meta/downsample"] = np.int64(lss.downsample)
+    out["meta/features"], out["meta/depth_bins"] = np.int64(lss.camC), np.int64(lss.D)
+    out["meta/final_dim"] = np.asarray(lss.data_aug_conf["final_dim"], dtype=np.int64)
+    g = lss.grid_conf
+    for k in ("xbound", "ybound", "zbound", "ddiscr"):
+        out["meta/grid/" + k] = np.asarray(g[k], dtype=np.float64)
+    out["meta/grid/mode"] = np.array(str(g["mode"]))
+    return check_finite(out)
