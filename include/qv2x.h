@@ -43,7 +43,8 @@ const char* qv2x_last_error(void);
  * 9 = qv2x_voxelize_batch_f32 / qv2x_postprocess_batch_f32 and their workspace queries added, no struct changed.  The detection-evaluation
  * entries (qv2x_eval_desc, qv2x_eval_workspace_bytes, qv2x_eval_tp_fp_f32) and the ground-truth entry (qv2x_gt_desc, qv2x_gt_boxes_f32)
  * joined under 9: nothing that existed changed, and a caller that needs them finds out by looking the symbol up.  So did the PTQ
- * range search (qv2x_range_search_desc, qv2x_range_search_workspace_bytes, qv2x_range_search_f32): additions only, the value stays 9. */
+ * range search (qv2x_range_search_desc, qv2x_range_search_workspace_bytes, qv2x_range_search_f32): additions only, the value stays 9.
+ * So did the span pair of the two-stage encode (qv2x_codebook_encode_candidates_span_i8, qv2x_codebook_encode_span_f32). */
 #define QV2X_ABI_VERSION 9
 int qv2x_version(void);            /* == QV2X_ABI_VERSION of the library's own build */
 
@@ -315,6 +316,30 @@ int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* desc /* host */, con
 int qv2x_codebook_encode_candidates_seg_i8(const qv2x_encode_desc* desc /* host */, const int8_t* in, const int8_t* g_limbs, const double* bias_packed,
                                            const int32_t* tables, const float* tau /* host */, uint8_t* codes, uint32_t* list, uint32_t* counters,
                                            void* stream);
+
+/* The SPAN form of the two-stage encode: the same indices, with stage 2 ending a tile of listed cells at their last undecided level.  The
+ * four entries above keep their contract, their lists and their counters; these two are a pair of their own with buffers of their own.
+ *
+ * Stage 1, qv2x_codebook_encode_candidates_span_i8: the kernel of the two candidate entries, every shape they take (seg_num 1 | 2,
+ * dict_size up to 256, up to three levels), the same operands -- bias_packed with 128 where seg_num is 1 and dict_size <= 128, with 256
+ * otherwise -- the same codes and the same cells listed.  It also keeps the LAST level a cell is undecided at (a level is undecided if any of
+ * its segments is) and files the cell under its (first, last) class, dearest class of stage 2 first:
+ *     class   0       1       2       3       4       5
+ *     (f, l)  (0, 2)  (1, 2)  (2, 2)  (0, 1)  (1, 1)  (0, 0)
+ *   list u32 [6][n*h*w]: list k = the cells of class k, in no particular order; counters u32 [8]: [0] all listed cells, [1 + k] the length
+ *   of list k, [7] unused -- DEVICE, zeroed by this call (a kernel node under stream capture)
+ * Stage 2, qv2x_codebook_encode_span_f32 (`list`, `list_count` = stage 1's `list`, `counters`): the listed cells are one sequence, list 0
+ * first, cut into tiles of 32.  A tile starts at the smallest `first` of its cells (levels below it: the stored code, as
+ * qv2x_codebook_encode_listed_f32) and runs the chain, bit for bit, up to the argmin of its largest `last`.  There every cell compares the
+ * chain's index with the stored candidate at each level the tile computed (the candidate is read before it is overwritten).  All equal: the
+ * cells' stored later codes were proven by stage 1 on exactly these earlier codes, they ARE the chain's indices, and the tile is done.  Any
+ * cell differs: the whole tile runs every remaining level in full and overwrites the later codes.  The split between persistent waves and
+ * workgroups and the fixed launch sizes are those of qv2x_codebook_encode_listed_f32: capturable in a HIP graph. */
+int qv2x_codebook_encode_candidates_span_i8(const qv2x_encode_desc* desc /* host */, const int8_t* in, const int8_t* g_limbs, const double* bias_packed,
+                                            const int32_t* tables, const float* tau /* host */, uint8_t* codes, uint32_t* list, uint32_t* counters,
+                                            void* stream);
+int qv2x_codebook_encode_span_f32(const qv2x_encode_desc* desc /* host */, const int8_t* in, const float* const* level_weights /* host array */,
+                                  const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream);
 
 /* a7 + a8 + a9 + a10.  UMGMQuantizer.decode as three table look-ups (codebook.py:339-343; all heads affine),
  * warp_affine_simple (torch_transformation_utils.py:323-332: affine_grid + bilinear grid_sample, zeros,

@@ -44,8 +44,45 @@ __device__ __forceinline__ void list_tile(const ListPlan& p, int tile, int& cls,
     i0 = (tile - p.first[cls]) * 32;
 }
 
+// ---- the span form of stage 2 (qv2x_codebook_encode_span_f32; codebook_encode_cand.hip's span entry writes its lists) -----------------------
+// SIX lists by the (first, last) undecided level of a cell, dearest first by the work stage 2 spends on the class -- 2 f products of latent
+// chain in front, 2.5 per level f .. l (stage, qhead, distances), 1 per lhead in between:
+//     class   0       1       2       3       4       5
+//     (f, l)  (0, 2)  (1, 2)  (2, 2)  (0, 1)  (1, 1)  (0, 0)
+//     cost    9.5     8       6.5     6       4.5     2.5
+// List k at a.list + k * a.M, its length at a.list_count[1 + k] (a.list_count[0] = all of them).  The listed cells are ONE sequence -- list 0,
+// then list 1, ... -- cut into tiles of 32, so only a tile on a class boundary holds cells of two classes and only the last tile is partial.
+// Whole rounds / remainder: the rule of list_plan.
+constexpr int SPAN_CLASSES = 6;
+__device__ __host__ __forceinline__ constexpr int span_first(int k) { return k < 3 ? k : (k < 5 ? k - 3 : 0); }
+__device__ __host__ __forceinline__ constexpr int span_last(int k) { return k < 3 ? 2 : (k < 5 ? 1 : 0); }
+// (first, last) -> class; last >= first
+__device__ __host__ __forceinline__ constexpr int span_class(int first, int last) { return last == 2 ? first : (last == 1 ? 3 + first : 5); }
+struct SpanPlan { int pre[SPAN_CLASSES + 1], total, full; };          // pre[k]: listed cells in front of list k; total / full in tiles
+__device__ __forceinline__ SpanPlan span_plan(const EncArgs& a) {
+    SpanPlan p;
+    p.pre[0] = 0;
+#pragma unroll
+    for (int k = 0; k < SPAN_CLASSES; ++k) p.pre[k + 1] = p.pre[k] + (int)a.list_count[1 + k];
+    p.total = (p.pre[SPAN_CLASSES] + 31) >> 5;
+    const int full = p.total / a.list_slots * a.list_slots;
+    p.full = p.total - full > a.list_tail_max ? p.total : full;
+    return p;
+}
+// entry i of the sequence (clamped to the last one: a partial tile's idle lanes repeat it) -> the cell and its class
+__device__ __forceinline__ int span_cell(const SpanPlan& p, const EncArgs& a, int i, int& cls) {
+    i = i < p.pre[SPAN_CLASSES] ? i : p.pre[SPAN_CLASSES] - 1;
+    int base = 0;
+    cls = 0;
+#pragma unroll
+    for (int k = 1; k < SPAN_CLASSES; ++k)
+        if (i >= p.pre[k]) { cls = k; base = p.pre[k]; }
+    return (int)a.list[(size_t)cls * a.M + (i - base)];
+}
+
 // codebook_encode_wave.hip
 int encode_wave_launch(const EncArgs& a, hipStream_t st);      // rows [a.m_lo, a.m_hi): one wave per 32
 int encode_wave_list_launch(const EncArgs& a, int waves, hipStream_t st);   // the cells a.list[0 .. *a.list_count): persistent waves
+int encode_wave_span_launch(const EncArgs& a, int waves, hipStream_t st);   // the same on the six span lists, a tile ends at its last undecided level
 
 }  // namespace qv2x

@@ -149,9 +149,12 @@ template <int ER> constexpr int enc_smem_floats() { return 2 * ER * LDF + 4 * ER
 // and the per-segment bookkeeping cost the 32-row form 15 registers and 8 bytes of scratch under its 128-register bound, so they are
 // compiled out of the form every V2X-Real / OPV2V attfuse model takes; EXT = true: seg_num > 1 or an extended codebook of several rounds.
 // LIST (round 6): the rows are the listed cells a.list[m0 .. m0 + ER) (stage 2 of the two-stage encode), not the cells m0 .. m0 + ER.
-template <int ER, bool EXT, bool LIST = false>
+// SPAN (with LIST; codebook_encode_wave.hip has the rule): the rows may be done after the argmin of level `exitl` -- every row compares its
+// fp32 index with the stored candidate at the levels start .. exitl (read before it is overwritten) and raises `*differs` (LDS, zero on
+// entry) if they are not the same; nothing raised: the stored later codes stand and the rows are done; else they run on to the end.
+template <int ER, bool EXT, bool LIST = false, bool SPAN = false>
 __device__ __forceinline__ void encode_rows(const EncArgs& a, const int m0, float* __restrict__ smem, const unsigned* __restrict__ lst = nullptr,
-                                            const int n_listed = 0, const int start = 0) {
+                                            const int n_listed = 0, const int start = 0, const int exitl = -1, int* differs = nullptr) {
     constexpr int ERT = ER / 32;
     const int segs = EXT ? a.segs : 1;
     float* bufA = smem;                       // x, then q, then next x
@@ -368,12 +371,17 @@ __device__ __forceinline__ void encode_rows(const EncArgs& a, const int m0, floa
                 const int bi = (int)(unsigned)bk;                      // row of the extended codebook: sg * kc + code
                 code_s[sg * ER + tid] = bi;
                 if (LIST) {
-                    if (m0 + tid < n_listed) a.codes[((size_t)l * segs + sg) * a.M + lst[m0 + tid]] = (uint8_t)(bi - sg * a.kc);
+                    if (m0 + tid < n_listed) {
+                        uint8_t* at = a.codes + ((size_t)l * segs + sg) * a.M + lst[m0 + tid];
+                        if (SPAN && l <= exitl && (int)*at != bi - sg * a.kc) *differs = 1;
+                        *at = (uint8_t)(bi - sg * a.kc);
+                    }
                 } else if (m0 + tid < a.m_hi) a.codes[((size_t)l * segs + sg) * a.M + m0 + tid] = (uint8_t)(bi - sg * a.kc);
             }
         }
         lds_barrier();
         EFINE(9);
+        if (SPAN && l == exitl && !*differs) break;                     // (uniform: the flag was written before the barrier)
         }
 
         if (l + 1 < a.levels) {      // x <- lhead(z) - C[code]
@@ -424,6 +432,31 @@ __global__ __launch_bounds__(512, 2) void codebook_encode_list_tail_kernel(const
         int cls, i0;
         list_tile(plan, t, cls, i0);                                    // list c: the cells first undecided at level c
         encode_rows<32, EXT, true>(a, i0, smem, a.list + (size_t)cls * a.M, plan.n[cls], cls);
+        __syncthreads();
+    }
+}
+
+// The remainder of the SPAN lists (codebook_encode.h:span_plan): a tile's 32 cells are resolved into LDS first -- encode_rows then sees a list
+// of its own, `n` cells long -- with the tile's first level, its exit level and the flag its rows raise.
+template <bool EXT>
+__global__ __launch_bounds__(512, 2) void codebook_encode_span_tail_kernel(const EncArgs a) {
+    __shared__ __attribute__((aligned(16))) float smem[enc_smem_floats<32>()];
+    __shared__ unsigned cells[32];
+    __shared__ int span[2], differs;
+    const SpanPlan plan = span_plan(a);
+    for (int t = plan.full + (int)blockIdx.x; t < plan.total; t += (int)gridDim.x) {
+        if (threadIdx.x < 64) {                                         // (wave 0: lanes 32 .. 63 repeat 0 .. 31)
+            int cls;
+            const unsigned cell = (unsigned)span_cell(plan, a, t * 32 + ((int)threadIdx.x & 31), cls);
+            const int f = span_first(cls), e = span_last(cls);
+            const int start = __builtin_amdgcn_ballot_w64(f == 0) ? 0 : (__builtin_amdgcn_ballot_w64(f == 1) ? 1 : 2);
+            const int exitl = __builtin_amdgcn_ballot_w64(e == 2) ? 2 : (__builtin_amdgcn_ballot_w64(e == 1) ? 1 : 0);
+            if (threadIdx.x < 32) cells[threadIdx.x] = cell;
+            if (threadIdx.x == 0) { span[0] = start; span[1] = exitl; differs = 0; }
+        }
+        __syncthreads();
+        const int n = plan.pre[SPAN_CLASSES] - t * 32;
+        encode_rows<32, EXT, true, true>(a, 0, smem, cells, n < 32 ? n : 32, span[0], span[1], &differs);
         __syncthreads();
     }
 }
@@ -485,10 +518,27 @@ extern "C" int qv2x_codebook_encode_f32in(const qv2x_encode_desc* d, const float
 // Stage 2 of the two-stage exact encode (encode_two_stage.py, codebook_encode_cand.hip): qv2x_codebook_encode_f32's arithmetic on the cells
 // `list[0 .. *list_count)` only -- the count lives on the DEVICE (the candidate stage wrote it), the launch is a fixed number of persistent
 // waves, so the pair of launches is capturable in a HIP graph.
+static int encode_listed(const bool span, const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
+                         const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream);
+
 extern "C" int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
                                                const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream) {
+    return encode_listed(false, d, in, level_weights, list, list_count, codes, stream);
+}
+
+// The span form (include/qv2x.h): six lists by (first, last) undecided level, a tile of 32 listed cells ends at its last undecided level when
+// the chain has confirmed every stored candidate up to there.  Same split between persistent waves and workgroups, same fixed launches.
+extern "C" int qv2x_codebook_encode_span_f32(const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
+                                             const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream) {
+    if (d && d->levels > 3) return qv2x::fail(QV2X_EINVAL, "qv2x_codebook_encode_span_f32: up to three levels (the span lists have no class beyond level 2)");
+    return encode_listed(true, d, in, level_weights, list, list_count, codes, stream);
+}
+
+// (the messages name qv2x_codebook_encode_listed_f32 for both entries: the argument rules are its own)
+static int encode_listed(const bool span, const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
+                         const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream) {
     using namespace qv2x;
-    if (!d || !in || !level_weights || !codes || !list || !list_count) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: null pointer");
+    if (!d ||!in || !level_weights || !codes || !list || !list_count) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: null pointer");
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->levels < 1 || d->levels > 4) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: bad shape");
     const int segs = d->segs ? d->segs : 1;
     if (segs != 1 && segs != 2) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: seg_num 1 or 2 (got %d)", d->segs);
@@ -520,7 +570,7 @@ extern "C" int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* d, const 
     // of a one-frame graph even when it finds nothing to do.
     const int grid_tail = 2 * cus;
     if (tiles + 3 >= 2 * a.list_slots) {
-        if (int rc = encode_wave_list_launch(a, a.list_slots, (hipStream_t)stream)) return rc;
+        if (int rc = span ? encode_wave_span_launch(a, a.list_slots, (hipStream_t)stream) : encode_wave_list_launch(a, a.list_slots, (hipStream_t)stream)) return rc;
     } else {
         a.list_slots = 1 << 30; a.list_tail_max = 1 << 30;
     }
@@ -528,7 +578,10 @@ extern "C" int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* d, const 
     // slower: 145 against 97 us for one frame, 1164 against 940 us at the batch.  Every workgroup streams the same 2.7 MB of weights, and what
     // the launch waits for is that stream (~3-4 TB/s over the chip whatever the prefetch depth), not the matrix pipe:
     // tools/probes/codebook_encode_tail16_experiment.hip, profiles/r06_tail16_experiment.log)
-    if (ext) codebook_encode_list_tail_kernel<true><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
+    if (span) {
+        if (ext) codebook_encode_span_tail_kernel<true><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
+        else codebook_encode_span_tail_kernel<false><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
+    } else if (ext) codebook_encode_list_tail_kernel<true><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
     else codebook_encode_list_tail_kernel<false><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
     return hip_check(hipGetLastError(), "qv2x_codebook_encode_listed_f32 launch");
 }

@@ -57,8 +57,14 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int m) {
     return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
 }
 
-template <int CT, int SEGS, int PACK>
+// SPAN (qv2x_codebook_encode_candidates_span_i8): the wave also keeps the LAST level a cell is undecided at, and the listed cells go to SIX
+// lists by (first, last) -- span_class below, the order of codebook_encode.h:span_plan: dearest class of stage 2 first -- with seven counters.
+// Nothing else differs: the same scores, the same codes, the same cells listed.
+__device__ __forceinline__ int span_class(int first, int last) { return last == 2 ? first : (last == 1 ? 3 + first : 5); }
+
+template <int CT, int SEGS, int PACK, bool SPAN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void encode_candidates_kernel(const CandArgs a) {
+    constexpr int NC = SPAN ? 6 : 3;                                 // lists
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 31, hf = lane >> 5;
     const int m0 = ((int)blockIdx.x * 4 + wave) * (32 * CT);
     // (a wave past the last cell walks on with clamped cells and stores nothing: the workgroup meets at a barrier at the end)
@@ -106,6 +112,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.tables, 0, a.tbytes, 0x00020000);
     int o[2][SEGS][CT] = {};                                         // byte offsets of the cells' table rows: ((s' kc + code_{j, s'}) * ke + 4 hf) * 4
     int first[CT];                                                   // the level a cell is first undecided at (3: never)
+    int lastw[SPAN ? CT : 1];                                        // SPAN: ... and last undecided at
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) first[ct] = 3;
     const int ntile = a.kc >> 5;                                     // score tiles per segment
@@ -202,8 +209,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         segment(IC<0>{});
         if constexpr (SEGS > 1) segment(IC<1>{});
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
+        for (int ct = 0; ct < CT; ++ct) {
             if (weak_l[ct] && first[ct] == 3) first[ct] = l;           // a level is undecided if any of its segments is
+            if constexpr (SPAN) lastw[ct] = (weak_l[ct] || l == 0) ? l : lastw[ct];
+        }
     };
     level(IC<0>{});
     if (a.levels > 1) level(IC<1>{});
@@ -213,37 +222,49 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     //      head and the distances of those levels for it (codebook_encode_wave.hip).  No particular order inside a list. ------------------
     // (ONE returning atomic per list and wave, the three issued together: a returning atomic is a whole L2 round trip for a lone wave, and a
     //  first version with one per list and cell tile -- twelve, each behind a branch -- cost the kernel 15 %)
-    unsigned long long mask[3][CT];
-    unsigned cnt[3] = {0, 0, 0};
+    // (SPAN: the list of a cell is its (first, last) class -- six lists, the same reservation: one returning atomic per list and workgroup)
+    int cls[CT];                                                     // the cell's list (NC: none)
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
+    for (int ct = 0; ct < CT; ++ct) {
+        if constexpr (SPAN) cls[ct] = first[ct] == 3 ? NC : span_class(first[ct], lastw[ct]);
+        else cls[ct] = first[ct] == 3 ? NC : first[ct];
+    }
+    unsigned long long mask[NC][CT];
+    unsigned cnt[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        cnt[c] = 0;
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
-            mask[c][ct] = __builtin_amdgcn_ballot_w64(first[ct] == c && hf == 0 && m[ct] < a.M);
+            mask[c][ct] = __builtin_amdgcn_ballot_w64(cls[ct] == c && hf == 0 && m[ct] < a.M);
             cnt[c] += (unsigned)__builtin_popcountll(mask[c][ct]);
         }
+    }
     // ... and one per list and WORKGROUP: the waves' counts meet in LDS, wave 0 reserves the workgroup's ranges
-    __shared__ unsigned wcnt[4][3], wbase[3];
-    if (lane == 0) { wcnt[wave][0] = cnt[0]; wcnt[wave][1] = cnt[1]; wcnt[wave][2] = cnt[2]; }
+    __shared__ unsigned wcnt[4][NC], wbase[NC];
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) wcnt[wave][c] = cnt[c];
+    }
     __syncthreads();
-    if (threadIdx.x < 3) {
+    if (threadIdx.x < NC) {
         const unsigned tot = wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x] + wcnt[2][threadIdx.x] + wcnt[3][threadIdx.x];
         wbase[threadIdx.x] = tot ? atomicAdd(a.counters + 1 + threadIdx.x, tot) : 0u;
         if (tot) atomicAdd(a.counters, tot);
     }
     __syncthreads();
-    unsigned base[3];
+    unsigned base[NC];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < NC; ++c) {
         base[c] = wbase[c];
         for (int w2 = 0; w2 < wave; ++w2) base[c] += wcnt[w2][c];
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < NC; ++c) {
         unsigned at = __builtin_amdgcn_readfirstlane(base[c]);
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
-            if (first[ct] == c && hf == 0 && m[ct] < a.M)
+            if (cls[ct] == c && hf == 0 && m[ct] < a.M)
                 a.list[(size_t)c * a.M + at + (unsigned)__builtin_popcountll(mask[c][ct] & ((1ull << lane) - 1ull))] = (unsigned)m[ct];
             at += (unsigned)__builtin_popcountll(mask[c][ct]);
         }
@@ -251,15 +272,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 // (a kernel, not hipMemsetAsync: every clear of this library is a kernel node under stream capture)
-__global__ void zero_counters_kernel(unsigned* c) { if (threadIdx.x < 4) c[threadIdx.x] = 0; }
+__global__ void zero_counters_kernel(unsigned* c, int n) { if ((int)threadIdx.x < n) c[threadIdx.x] = 0; }
 
-template <int CT, int SEGS, int PACK>
+template <int CT, int SEGS, int PACK, bool SPAN>
 void launch(const CandArgs& a, hipStream_t st) {
-    encode_candidates_kernel<CT, SEGS, PACK><<<(a.M + 128 * CT - 1) / (128 * CT), 256, 0, st>>>(a);
+    encode_candidates_kernel<CT, SEGS, PACK, SPAN><<<(a.M + 128 * CT - 1) / (128 * CT), 256, 0, st>>>(a);
 }
 
-// Both entries: PACK is the entry's packing factor and its largest dict_size (the index has log2 PACK bits), MAX_SEGS its largest seg_num.
-template <int PACK, int MAX_SEGS>
+// All entries: PACK is the entry's packing factor and its largest dict_size (the index has log2 PACK bits), MAX_SEGS its largest seg_num;
+// SPAN: six lists by (first, last) undecided level and seven counters (eight are zeroed).
+template <int PACK, int MAX_SEGS, bool SPAN = false>
 int candidates(const char* me, const qv2x_encode_desc* d, const int8_t* in, const int8_t* g_limbs, const double* bias_packed, const int32_t* tables,
                const float* tau, uint8_t* codes, uint32_t* list, uint32_t* counters, void* stream) {
     if (!d || !in || !g_limbs || !bias_packed || !tau || !codes || !list || !counters) return fail(QV2X_EINVAL, "%s: null pointer", me);
@@ -282,13 +304,13 @@ int candidates(const char* me, const qv2x_encode_desc* d, const int8_t* in, cons
     a.tbytes = (d->levels > 1 ? d->levels * (d->levels - 1) / 2 : 1) * a.ke * a.ke * 4;
     a.delta = d->in_delta;
     hipStream_t st = (hipStream_t)stream;
-    zero_counters_kernel<<<1, 64, 0, st>>>(counters);
+    zero_counters_kernel<<<1, 64, 0, st>>>(counters, SPAN ? 8 : 4);
     int dev = 0, cus = 256, v = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
     // the large tile (4 at one segment, 3 at two) from two rounds of its waves on every SIMD of the chip, the 64-cell wave below
     const bool large = a.M >= 4 * cus * 32 * (segs == 2 ? 3 : 4) * 2;
-    if (segs == 1) large ? launch<4, 1, PACK>(a, st) : launch<2, 1, PACK>(a, st);
-    else if constexpr (MAX_SEGS > 1) large ? launch<3, 2, PACK>(a, st) : launch<2, 2, PACK>(a, st);
+    if (segs == 1) large ? launch<4, 1, PACK, SPAN>(a, st) : launch<2, 1, PACK, SPAN>(a, st);
+    else if constexpr (MAX_SEGS > 1) large ? launch<3, 2, PACK, SPAN>(a, st) : launch<2, 2, PACK, SPAN>(a, st);
     return hip_check(hipGetLastError(), me);
 }
 
@@ -305,4 +327,15 @@ extern "C" int qv2x_codebook_encode_candidates_seg_i8(const qv2x_encode_desc* d,
                                                       const int32_t* tables, const float* tau, uint8_t* codes, uint32_t* list, uint32_t* counters,
                                                       void* stream) {
     return qv2x::candidates<256, 2>("qv2x_codebook_encode_candidates_seg_i8", d, in, g_limbs, bias_packed, tables, tau, codes, list, counters, stream);
+}
+
+// The span form of stage 1 for every shape of the two entries above: bias packed with 128 where seg_num is 1 and dict_size <= 128 (the
+// operands of qv2x_codebook_encode_candidates_i8), with 256 otherwise (those of qv2x_codebook_encode_candidates_seg_i8).
+extern "C" int qv2x_codebook_encode_candidates_span_i8(const qv2x_encode_desc* d, const int8_t* in, const int8_t* g_limbs, const double* bias_packed,
+                                                       const int32_t* tables, const float* tau, uint8_t* codes, uint32_t* list, uint32_t* counters,
+                                                       void* stream) {
+    const char* me = "qv2x_codebook_encode_candidates_span_i8";
+    if (d && (d->segs ? d->segs : 1) == 1 && d->kc <= 128)
+        return qv2x::candidates<128, 1, true>(me, d, in, g_limbs, bias_packed, tables, tau, codes, list, counters, stream);
+    return qv2x::candidates<256, 2, true>(me, d, in, g_limbs, bias_packed, tables, tau, codes, list, counters, stream);
 }

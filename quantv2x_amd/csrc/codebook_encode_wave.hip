@@ -81,13 +81,22 @@ template <int V> struct IC { static constexpr int value = V; };
 // LIST (round 6, stage 2 of the two-stage exact encode -- encode_two_stage.py): the wave's cells are `a.list[32 tile + j]`, tile = blockIdx.x,
 // blockIdx.x + gridDim.x, ... below ceil(*a.list_count / 32) -- a persistent launch of fixed size whose work is a DEVICE-side count (the cells
 // the candidate stage could not decide), so the whole encode stays capturable in a HIP graph.  The arithmetic is untouched.
-template <bool F32IN, int SEGS, bool LIST = false>
+// SPAN (with LIST; stage 2 behind qv2x_codebook_encode_span_f32): the cells come in six lists by their (first, last) undecided level
+// (codebook_encode.h:span_plan).  A tile starts at the smallest `first` of its cells and EXITS after the argmin of the largest `last`: if the
+// fp32 chain reproduced the stored candidate of every cell at every level it computed there (one ballot), the cells' stored later codes are
+// PROVEN -- the proof of a later level only needs the earlier codes to be the ones stage 1 used -- and the tile is done: no lhead, no later
+// level, the weight stream stops.  If any cell differs, the whole tile goes on through every remaining level in full, as a tile of list
+// `first` does without SPAN, and overwrites the later codes.  The arithmetic of the levels that run is untouched.
+template <bool F32IN, int SEGS, bool LIST = false, bool SPAN = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(1, 1))) void codebook_encode_wave_kernel(const EncArgs a) {
+    static_assert(LIST || !SPAN, "the span form is a list form");
     __shared__ __attribute__((aligned(16))) float smem[32 * RS];
     const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
     float* const row = smem + j * RS;
     ListPlan plan{};
-    if (LIST) plan = list_plan(a);
+    SpanPlan splan{};
+    if (LIST && !SPAN) plan = list_plan(a);
+    if (SPAN) { splan = span_plan(a); plan.full = splan.full; }
     // LIST: rounds of gridDim.x tiles, every second round walked BACKWARDS -- the tiles are numbered list by list (dearest first: a tile of
     // list 0 runs the whole chain, of list 2 seven of its eleven products), so a wave that took a dear tile in one round takes a cheap one in
     // the next (forwards only: the first waves got list 0 + list 1, the last list 1 + list 2)
@@ -97,8 +106,16 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_
     if (LIST && tile >= plan.full) continue;
     int mrow;                                                        // this lane's cell, and whether its codes are stored
     bool owned;
+    int exitl = -1;                                                  // SPAN: the level after whose argmin the tile may be done (-1: none, run to the end)
     int start = 0;                                                   // LIST: the cells' codes below this level are PROVEN (the candidate stage accepted them):
-    if (LIST) {                                                      // their quantization head, |q|^2 and distances are skipped, the stored code is used
+    if constexpr (SPAN) {                                            // their quantization head, |q|^2 and distances are skipped, the stored code is used
+        int cls;
+        mrow = span_cell(splan, a, tile * 32 + j, cls);
+        owned = tile * 32 + j < splan.pre[SPAN_CLASSES];
+        const int f = span_first(cls), e = span_last(cls);             // (an idle lane repeats the last cell: its class too)
+        start = __builtin_amdgcn_ballot_w64(f == 0) ? 0 : (__builtin_amdgcn_ballot_w64(f == 1) ? 1 : 2);
+        exitl = __builtin_amdgcn_ballot_w64(e == 2) ? 2 : (__builtin_amdgcn_ballot_w64(e == 1) ? 1 : 0);
+    } else if (LIST) {
         int cls, i0;
         list_tile(plan, tile, cls, i0);
         owned = i0 + j < plan.n[cls];
@@ -141,6 +158,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_
         }
     }
 
+    bool differs = false;                                           // SPAN: this cell's fp32 index left the stored candidate at a level up to `exitl`
     for (int l = 0; l < a.levels; ++l) {
         const float* W = a.lvl[l];
         const float* stage_b = W + D * D;
@@ -261,6 +279,11 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_
 #pragma unroll
             for (int sg = 0; sg < SEGS; ++sg) bcs |= (unsigned)a.codes[((size_t)l * SEGS + sg) * a.M + mrow] << (8 * sg);
         } else {
+        unsigned cand = 0;                                              // SPAN: the stored candidate, read BEFORE the argmin below overwrites it
+        if (SPAN && l <= exitl) {
+#pragma unroll
+            for (int sg = 0; sg < SEGS; ++sg) cand |= (unsigned)a.codes[((size_t)l * SEGS + sg) * a.M + mrow] << (8 * sg);
+        }
         // ---- q = qhead(z) -------------------------------------------------------------------------------------------------
 #pragma unroll 1
         for (int P = 0; P < 4; ++P) {
@@ -382,9 +405,13 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_
             if constexpr (SEGS == 2) seg_pairs(IC<0>{}, IC<1>{}, false);
             else { seg_pairs(IC<0>{}, IC<1>{}, true); seg_pairs(IC<2>{}, IC<3>{}, false); }
         }
+        if (SPAN && l <= exitl) differs |= bcs != cand;
         }                                                               // (the level's code was computed, not taken over)
         WFINE(5);
         if (last) break;
+        // every candidate confirmed: the stored later codes are the chain's own.  Else a prefix changed and nothing proves the later codes of
+        // this tile: it runs on in full (l > exitl from here: no further comparison, no further exit)
+        if (SPAN && l == exitl && !__builtin_amdgcn_ballot_w64(differs)) break;
         // ---- x <- lhead(z) - C[code] ------------------------------------------------------------------------------------------
 #pragma unroll 1
         for (int P = 0; P < 4; ++P) {
@@ -430,6 +457,14 @@ int encode_wave_list_launch(const EncArgs& a, int waves, hipStream_t st) {
     if (a.segs == 2) codebook_encode_wave_kernel<false, 2, true><<<(unsigned)waves, 64, 0, st>>>(a);
     else codebook_encode_wave_kernel<false, 1, true><<<(unsigned)waves, 64, 0, st>>>(a);
     return hip_check(hipGetLastError(), "qv2x_codebook_encode_listed_f32 launch");
+}
+
+// the same on the six span lists (codebook_encode.h:span_plan): a tile ends at its cells' last undecided level
+int encode_wave_span_launch(const EncArgs& a, int waves, hipStream_t st) {
+    if ((a.segs != 1 && a.segs != 2) || a.in_f32) return fail(QV2X_EINVAL, "qv2x_codebook_encode_span_f32: seg_num 1 | 2, i8 rows");
+    if (a.segs == 2) codebook_encode_wave_kernel<false, 2, true, true><<<(unsigned)waves, 64, 0, st>>>(a);
+    else codebook_encode_wave_kernel<false, 1, true, true><<<(unsigned)waves, 64, 0, st>>>(a);
+    return hip_check(hipGetLastError(), "qv2x_codebook_encode_span_f32 launch");
 }
 
 }  // namespace qv2x

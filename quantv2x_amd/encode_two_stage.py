@@ -266,3 +266,54 @@ def candidate_emulate(codes_u8: np.ndarray, tabs: Dict[str, np.ndarray], in_delt
             flags[p] = (P * second + k2) - (P * best + out[p]) <= P * np.ceil(t) + (P - 1.0)
             gaps[p] = (second - best) * h
     return out, flags.any(0), flags, gaps
+
+
+# ---- the span form of stage 2 (csrc/codebook_encode.h:span_plan, include/qv2x.h) --------------------------------------------------------------
+# A listed cell is filed under the (first, last) level it is undecided at; the lists come dearest class of stage 2 first.
+SPAN_CLASSES = ((0, 2), (1, 2), (2, 2), (0, 1), (1, 1), (0, 0))
+
+
+def span_cost(first: int, last: int) -> float:
+    """stage 2's work on a cell that starts at ``first`` and ends after the distances of ``last``, a 256-wide product = 1: the latent chain in
+    front (stage + lhead per level), then stage, qhead and the distances (0.5) per level, an lhead between two of them"""
+    return 2.0 * first + 2.5 * (last - first + 1) + (last - first)
+
+
+def span_classes(flags: np.ndarray, segs: int = 1):
+    """``candidate_emulate``'s per-plane flags bool [levels * segs, R] -> (first, last, cls) int [R]: the first and the last level a cell is
+    undecided at (a level is undecided if any of its segments is) and its index in SPAN_CLASSES; -1 everywhere for a cell that is not listed"""
+    lev = flags.reshape(flags.shape[0] // segs, segs, -1).any(1)
+    levels = lev.shape[0]
+    listed = lev.any(0)
+    first = np.where(listed, lev.argmax(0), -1)
+    last = np.where(listed, levels - 1 - lev[::-1].argmax(0), -1)
+    cls = np.full(first.shape, -1)
+    for k, (f, e) in enumerate(SPAN_CLASSES):
+        cls[(first == f) & (last == e)] = k
+    return first, last, cls
+
+
+def span_rule(cand: np.ndarray, flags: np.ndarray, chain: np.ndarray, segs: int = 1):
+    """The exit / continue rule of the span form, cell by cell.  ``cand``: stage 1's codes u8 [levels * segs, R]; ``flags``: its per-plane
+    flags; ``chain``: the fp32 chain's codes (the oracle's, or the exact kernel's), read ONLY where the rule has stage 2 compute them.
+
+    A cell of class (f, l) keeps the stored codes below f, takes the chain's from f to l, and compares them there with the candidates.  All
+    equal: it EXITS and keeps the stored codes behind l -- stage 1 proved them on exactly these earlier codes.  Any differs: it CONTINUES and
+    takes the chain's codes to the end.  (The chain's index at a level is the oracle's as long as every earlier code is the oracle's: below f
+    by stage 1's proof, from f on because they were just taken from it.)  Returns (codes, exited bool [R], work, work_before): the work in
+    ``span_cost`` units with the rule and with every listed cell run to the last level."""
+    levels = cand.shape[0] // segs
+    first, last, _ = span_classes(flags, segs)
+    out = cand.copy()
+    exited = np.zeros(cand.shape[1], bool)
+    work = before = 0.0
+    for r in np.nonzero(first >= 0)[0]:
+        f, e = int(first[r]), int(last[r])
+        span = slice(f * segs, (e + 1) * segs)
+        out[span, r] = chain[span, r]
+        exited[r] = bool((chain[span, r] == cand[span, r]).all())
+        if not exited[r]:
+            out[(e + 1) * segs:, r] = chain[(e + 1) * segs:, r]
+        before += span_cost(f, levels - 1)
+        work += span_cost(f, e if exited[r] else levels - 1)
+    return out, exited, work, before

@@ -963,6 +963,10 @@ class DeployedModel(DeployedPostStage):
         self._collapsed, self._two_stage, self.two_stage_refused = None, None, None
         self.encode_form = "auto"                                      # "wave": force the wave-per-32-cells encode kernel on every cell (same codes)
         self.encode_mode = "two_stage" if self.two_stage_supported() else "exact"
+        # the pair of entries behind "two_stage".  True: the span pair (qv2x_codebook_encode_candidates_span_i8 + qv2x_codebook_encode_span_f32:
+        # six lists by (first, last) undecided level, stage 2 ends a tile at its last undecided level -- DESIGN.md 3.1); False: the
+        # first pair (three lists by first undecided level, every listed cell through all later levels).  The same indices either way.
+        self.encode_span = True
 
     def _padded(self, n, h, w, c, q):
         """Padded i8 BEV tensor with the border (and interior) preset to the code of 0.0."""
@@ -1017,6 +1021,8 @@ class DeployedModel(DeployedPostStage):
                 self._build_two_stage()                                 # (a6's operands exist before a6 first runs)
             b["enc_list"] = torch.zeros(3 * n * hw, dtype=torch.int32, device=self.dev)     # three lists (by first undecided level)
             b["enc_counters"] = torch.zeros(4, dtype=torch.int32, device=self.dev)
+            b["enc_span_list"] = torch.zeros(6 * n * hw, dtype=torch.int32, device=self.dev)     # the span pair's own: six lists by (first, last)
+            b["enc_span_counters"] = torch.zeros(8, dtype=torch.int32, device=self.dev)
         if not self.has_codebook or self.heads_single is not None:
             b["feats"] = torch.empty((n, hw, 256), dtype=torch.float32, device=self.dev)
         self._bufs[n] = b
@@ -1265,6 +1271,13 @@ class DeployedModel(DeployedPostStage):
         """a6 as two launches (encode_two_stage.py): the candidate stage (``candidate_entry``) decides every cell it can PROVE, the listed
         rest goes through the reference-order kernel (qv2x_codebook_encode_listed_f32) -- identical indices, a fraction of the fp32 work."""
         gp, bias, tab, tau, _ = self._two_stage
+        if self.encode_span:                                           # the same operands: the span entry packs as candidate_entry() does
+            L.check(self.lib.qv2x_codebook_encode_candidates_span_i8(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
+                                                                     L.ptr(b["enc_span_list"]), L.ptr(b["enc_span_counters"]), L.current_stream()),
+                    "qv2x_codebook_encode_candidates_span_i8")
+            L.check(self.lib.qv2x_codebook_encode_span_f32(C.byref(d), L.ptr(b["s1"]), self.level_ptrs, L.ptr(b["enc_span_list"]),
+                                                           L.ptr(b["enc_span_counters"]), L.ptr(codes), L.current_stream()), "qv2x_codebook_encode_span_f32")
+            return codes
         name = self.candidate_entry()
         L.check(getattr(self.lib, name)(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
                                         L.ptr(b["enc_list"]), L.ptr(b["enc_counters"]), L.current_stream()), name)
@@ -1277,8 +1290,14 @@ class DeployedModel(DeployedPostStage):
         if not (self.encode_mode == "two_stage" and self.encode_form == "auto") or "enc_counters" not in self._bufs.get(n_agents, {}):
             raise L.Qv2xError(f"encode_refine_stats({n_agents}): no two-stage encode of {n_agents} frames here (encode_mode "
                               f"{self.encode_mode!r}, encode_form {self.encode_form!r}, workspaces {sorted(self._bufs)})")
-        c = self._bufs[n_agents]["enc_counters"].cpu().numpy().astype(np.int64)
         cells = n_agents * self.fh * self.fw
+        if self.encode_span:                                           # six classes (first, last), in the lists' order (encode_two_stage.SPAN_CLASSES)
+            from .encode_two_stage import SPAN_CLASSES
+            c = self._bufs[n_agents]["enc_span_counters"].cpu().numpy().astype(np.int64)
+            first = [int(sum(c[1 + k] for k, (f, _) in enumerate(SPAN_CLASSES) if f == l)) for l in range(self.enc_levels)]
+            return {"cells": cells, "refined": int(c[0]), "refined_fraction": float(c[0]) / cells, "first_flagged_at_level": first,
+                    "undecided_span": {f"{f}-{e}": int(c[1 + k]) for k, (f, e) in enumerate(SPAN_CLASSES)}}
+        c = self._bufs[n_agents]["enc_counters"].cpu().numpy().astype(np.int64)
         return {"cells": cells, "refined": int(c[0]), "refined_fraction": float(c[0]) / cells, "first_flagged_at_level": [int(v) for v in c[1:1 + self.enc_levels]]}
 
     def encode_into(self, inputs: dict, frames: int, codes_out: torch.Tensor):

@@ -44,6 +44,13 @@ def main():
                                                                  L.ptr(codes), L.current_stream()), "s2")
     s1(); torch.cuda.synchronize()
     print(f"stage 1 {bench.event_time_us(s1, 20):.1f} us, stage 2 {bench.event_time_us(s2, 20):.1f} us")
+    # the span pair by itself (its own lists; stage 2 alone repeats on codes that are final: every tile exits at its last undecided level)
+    s1s = lambda: L.check(eng.lib.qv2x_codebook_encode_candidates_span_i8(C.byref(d), L.ptr(b["s1"]), L.ptr(gp), L.ptr(bias), L.ptr(tab), tau, L.ptr(codes),
+                                                                          L.ptr(b["enc_span_list"]), L.ptr(b["enc_span_counters"]), L.current_stream()), "s1 span")
+    s2s = lambda: L.check(eng.lib.qv2x_codebook_encode_span_f32(C.byref(d), L.ptr(b["s1"]), eng.level_ptrs, L.ptr(b["enc_span_list"]),
+                                                                L.ptr(b["enc_span_counters"]), L.ptr(codes), L.current_stream()), "s2 span")
+    s1s(); torch.cuda.synchronize()
+    print(f"span pair: stage 1 {bench.event_time_us(s1s, 20):.1f} us, stage 2 {bench.event_time_us(s2s, 20):.1f} us")
 
 if not (len(sys.argv) > 2 and sys.argv[2] == "levels"):
     main()
