@@ -987,6 +987,35 @@ typedef struct {
 int qv2x_cam_heads_i8(const qv2x_cam_heads_desc* desc /* host */, const int8_t* in, const int8_t* w_frag, const float* scale,
                       const int32_t* corr, const int32_t* aw, const float* bias, float* depth, float* feats, void* stream);
 
+/* ---- camera agents: the input side of the first QuantBasicBlock of a camera agent's ResNetBEVBackbone on the lift-splat's fp32 BEV ------
+ * (quant_block.py:68-97: conv1 -> ReLU -> activation quantizer; the shortcut feeds the block's fp32 add).  One launch, both outputs from one
+ * read of the map.  quantv2x_amd/camera_bev.py states it in numpy over the CPU checker (bev_entry_statement); DESIGN.md section 15.
+ *   in        f32 [n][cin][h][w]: what qv2x_lss_splat_f32 writes, no transpose between;  ho = (h - 1) / stride + 1, wo likewise
+ *   w1        f32 [9 * cin / 8][cout][2][4]: element [g][co][p][j] = fl((code - zw[co]) * dw[co]) of conv1's weight at
+ *             k = 8 g + 2 j + p, k = (ky * 3 + kx) * cin + ci;   b1 f32 [cout]
+ *   conv1     per output: acc = +0; for k ascending acc = fmaf(x[ci][stride * yo + ky - 1][stride * xo + kx - 1], w[k][co], acc), taps outside
+ *             the map as x = 0;  y = acc + b1[co]
+ *   code      clamp(rint(fma(max(y, 0), fl(1 / out_delta), out_zp)), 0, 255): the epilogue of qv2x_deconv_f32in with relu = 1
+ *   out       padded i8 BEV [n][ho + 2][wo + 2][cout] as code - 128; the interior is written, the ring keeps its bytes
+ *   shortcut  f32 rows [n * ho * wo][cout] (qv2x_conv3x3_i8_res res_mode 2):
+ *             downsample = 1: acc = +0; for ci ascending acc = fmaf(x[ci][stride * yo][stride * xo], wd[ci][co], acc); row = acc + bd[co]
+ *                             with wd f32 [cin / 8][cout][2][4] laid out as w1 (k = ci), bd f32 [cout];  no ReLU, no quantizer
+ *             downsample = 0: the pixel's own channels x[co][yo][xo], copied (stride 1 and cin == cout, else QV2X_EINVAL); wd, bd ignored
+ * QV2X_EINVAL: a null pointer (wd, bd only when downsample = 1); n, h, w < 1; stride outside {1, 2}; downsample outside {0, 1}; cin < 16 or
+ * cout < 64; out_delta not > 0; out_zp outside 0..255; 4 * cin * (31 * stride + 3) > 65536 (one input row of a 32-pixel tile in LDS: cin up to
+ * 240 at stride 2, 480 at stride 1); ho or n * cout / 64 above 65535 or a tensor outside int32.  QV2X_EALIGN: cin % 16 or cout % 64 not 0; a
+ * pointer not 16-byte aligned.  Non-finite inputs: undefined codes where they reach. */
+typedef struct {
+    int32_t n, h, w;            /* samples; rows and columns of the input map */
+    int32_t cin, cout;          /* cin % 16 == 0, cout % 64 == 0 */
+    int32_t stride;             /* 1 | 2: conv1's and the downsample's */
+    int32_t downsample;         /* 1: the 1x1 downsample; 0: identity shortcut */
+    int32_t reserved;           /* 0 */
+    float out_delta, out_zp;    /* conv1's activation quantizer */
+} qv2x_bev_entry_desc;
+int qv2x_bev_entry_f32(const qv2x_bev_entry_desc* desc /* host */, const float* in, const float* w1, const float* b1, const float* wd,
+                       const float* bd, int8_t* out, float* shortcut, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -20,6 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
+from .ptq_state import CAMERA_PREFIX
+from .camera_bev import center_crop_window, crop_mask_statement, crop_target
 from .engine import (_ConvLayer, _DeconvLayer, _Heads, _dev, _pack_k4p, _pairwise_from_poses, assemble_heter_codes, capture_forward,
                      codebook_constants, pfn_params, pillar_inputs, scene_layout, split_heads)
 
@@ -116,6 +118,21 @@ class _Occ:
         self.occ_lut = _dev(self.occ_values, dev)
 
 
+class _CameraFirstBlock:
+    """The first QuantBasicBlock of a camera agent's backbone: its input is the lift-splat's fp32 BEV, so conv1 and the shortcut are ONE launch of
+    ``qv2x_bev_entry_f32`` (codes + fp32 shortcut rows); conv2 with the block's end in its epilogue runs on the int8 path as everywhere."""
+
+    def __init__(self, state, name, stride, dev):
+        from .camera_bev import BevEntry
+        self.name, self.stride, self.bottleneck, self.f32_input = name, stride, False, True
+        self.entry = BevEntry(state, name, stride, dev)
+        self.conv2 = _ConvLayer(state, name + ".conv2", [(0, self.entry.cout, self.entry.delta, self.entry.zp)], 1, dev)
+        self.cout = self.conv2.cout
+        self.conv1_q = (self.entry.delta, self.entry.zp)
+        self.down = None                                                 # (the shortcut lives in the entry launch)
+        self.in_q, self.out_q = None, _q(state, name)
+
+
 class _Block:
     """One residual block: its convolutions, optional strided shortcut, and the quantizer after the add."""
 
@@ -209,17 +226,39 @@ class DeployedPyramidModel(nn.Module):
         self.ratio = float(s["meta/discrete_ratio"])
         self.has_codebook = bool(s["meta/has_codebook"])            # heter_pyramid_collab_mc (LiDAROnly/lidar_pyramid.yaml): no codebook
 
-        self.pfn, q = pfn_params(s)
-
-        # ---- the agent's ResNet level ------------------------------------------------------------------------------------------
+        self.camera = str(s.get("meta/sensor_type", "lidar")) == "camera"
         nums, strides = [int(v) for v in s["meta/layer_nums"]], [int(v) for v in s["meta/layer_strides"]]
         self.agent_stride = strides[0]
         self.agent_blocks: List[_Block] = []
-        for b in range(nums[0]):
+        # camera agents' score masks: {modality: {"crop_ratio_H_<m>": .., "crop_ratio_W_<m>": ..}} as the reference's
+        # cam_crop_info; a camera state knows its own ratios, DeployedHeterPyramidModel gives the ego engine every camera modality's
+        self.cam_crop_info: Dict[str, Dict[str, float]] = {}
+        self._masks: Dict[tuple, List[torch.Tensor]] = {}
+        if self.camera:
+            # ---- a camera agent: images -> BEV (engine_camera) -> the first block's input side on the fp32 BEV (qv2x_bev_entry_f32) ----------
+            self.pfn = None
+            self.cam_state = {k[len(CAMERA_PREFIX):]: v for k, v in s.items() if k.startswith(CAMERA_PREFIX)}
+            self.cam_encoders: Dict[tuple, object] = {}
+            self.crop_ratio_h, self.crop_ratio_w = float(s["meta/crop_ratio_H"]), float(s["meta/crop_ratio_W"])
+            m = str(s.get("meta/modality", "m1"))
+            self.modality_names = [str(v) for v in s["meta/modality_names"]] if "meta/modality_names" in s else [m]
+            self.cam_crop_info[m] = {f"crop_ratio_W_{m}": self.crop_ratio_w, f"crop_ratio_H_{m}": self.crop_ratio_h}
+            first = _CameraFirstBlock(s, "backbone_m1.resnet.layer0.0", strides[0], dev)
+            if first.entry.cin != int(s["meta/canvas_channels"]):
+                raise ValueError(f"{first.name}.conv1 takes {first.entry.cin} channels, the camera's BEV has {int(s['meta/canvas_channels'])}")
+            self.agent_blocks.append(first)
+            q = first.out_q
+        else:
+            self.pfn, q = pfn_params(s)
+        # ---- the agent's ResNet level ------------------------------------------------------------------------------------------
+        for b in range(len(self.agent_blocks), nums[0]):
             blk = _Block(s, f"backbone_m1.resnet.layer0.{b}", q, strides[0] if b == 0 else 1, False, dev)
             self.agent_blocks.append(blk)
             q = blk.out_q
         self.agent_q = q
+        # the agents' feature map (h, w): the backbone's map, for a camera agent cropped / padded to the LiDAR range (_agent_ws: the same numbers)
+        mh, mw = (self.ny - 1) // self.agent_stride + 1, (self.nx - 1) // self.agent_stride + 1
+        self.feature_shape = (crop_target(mh, self.crop_ratio_h), crop_target(mw, self.crop_ratio_w)) if self.camera else (mh, mw)
         # ---- codebook (D = 64: its own encode kernel; other widths run the 256-wide one on zero-padded heads, engine.level_blob_host) --
         self.native64 = True
         if self.has_codebook:
@@ -286,15 +325,24 @@ class DeployedPyramidModel(nn.Module):
             return self._bufs[key]
         b = {}
         h, w, st = self.ny, self.nx, self.agent_stride
-        self.fh, self.fw = (h - 1) // st + 1, (w - 1) // st + 1
+        mh, mw = (h - 1) // st + 1, (w - 1) // st + 1                      # the backbone's map
+        if self.camera:
+            # the camera map is centre cropped / zero padded to the LiDAR range behind the backbone (heter_pyramid_collab.py:173-190)
+            self.mh, self.mw = mh, mw
+            self.fh, self.fw = crop_target(mh, self.crop_ratio_h), crop_target(mw, self.crop_ratio_w)
+        else:
+            self.fh, self.fw = mh, mw
         fh, fw = self.fh, self.fw
-        b["canvas"] = self._padded(n, h, w, 64, self.pfn.z2)
-        b["c1"] = self._padded(n, fh, fw, 64, self._same_zp([blk.conv1.out_q for blk in self.agent_blocks], "agent conv1"))
+        conv1_qs = [blk.conv1_q if isinstance(blk, _CameraFirstBlock) else blk.conv1.out_q for blk in self.agent_blocks]
+        if not self.camera:
+            b["canvas"] = self._padded(n, h, w, 64, self.pfn.z2)
+        b["c1"] = self._padded(n, mh, mw, 64, self._same_zp(conv1_qs, "agent conv1"))
         zp = self._same_zp([blk.out_q for blk in self.agent_blocks], "agent blocks")
-        b["x"] = [self._padded(n, fh, fw, 64, zp) for _ in range(2)]
-        # the last block writes channels [0, D); with the 256-wide encode kernel the rest stay at the code of 0.0
+        b["x"] = [self._padded(n, mh, mw, 64, zp) for _ in range(2)]
+        # the last block writes channels [0, D); with the 256-wide encode kernel the rest stay at the code of 0.0.  A camera agent's enc_in is
+        # filled with the block quantizer's zero point: the code of the 0.0 the reference pads with, exactly
         b["enc_in"] = self._padded(n, fh, fw, 64 if self.native64 else 256, zp)
-        b["ds"] = torch.empty((n * fh * fw, 64), dtype=torch.float32, device=self.dev)
+        b["ds"] = torch.empty((n * mh * mw, 64), dtype=torch.float32, device=self.dev)
         if self.has_codebook:
             b["codes"] = torch.empty((self.levels, n, fh * fw), dtype=torch.uint8, device=self.dev)
         self._bufs[key] = b
@@ -414,6 +462,58 @@ class DeployedPyramidModel(nn.Module):
                 "qv2x_pfn_scatter_i8")
         return canvas
 
+    def _camera_encoder(self, n: int, views: int):
+        from .engine_camera import DeployedCameraEncoder
+        enc = self.cam_encoders.get((n, views))
+        if enc is None:
+            enc = self.cam_encoders[(n, views)] = DeployedCameraEncoder(self.cam_state, views, n, self.dev)
+        return enc
+
+    def images_to_bev(self, inputs: dict, n: int):
+        """``inputs_<m>`` of a camera modality -> the lift-splat's BEV f32 [n, C * Z, Y, X]; the plan is made on every call (the matrices are
+        arguments here, as in ``heter_encoders.pool_bev``)"""
+        imgs = inputs["imgs"]
+        if imgs.dim() != 5 or imgs.shape[0] != n:
+            raise ValueError(f"inputs['imgs'] {tuple(imgs.shape)}: [{n}, views, 3 | 4, H, W] expected")
+        enc = self._camera_encoder(n, int(imgs.shape[1]))
+        enc.plan(*(inputs[k] for k in ("rots", "trans", "intrins", "post_rots", "post_trans")))
+        bev = enc(imgs)
+        if tuple(bev.shape[1:]) != (self.agent_blocks[0].entry.cin, self.ny, self.nx):
+            raise ValueError(f"the camera encoder's BEV is {tuple(bev.shape[1:])}, the state's grid says {(self.agent_blocks[0].entry.cin, self.ny, self.nx)}")
+        return bev
+
+    def camera_backbone(self, bev, n: int, taps: Optional[dict] = None):
+        """the BasicBlocks on the camera's BEV, then the crop / pad into ``enc_in``"""
+        b = self._agent_ws(n)
+        mh, mw = self.mh, self.mw
+        first = self.agent_blocks[0]
+        first.entry(bev, b["c1"], b["ds"])
+        x = b["x"][0]
+        self._conv3x3(first.conv2, b["c1"], n, mh, mw, x, first.out_q, 2, b["ds"])
+        xq = first.out_q
+        if taps is not None:
+            taps["bev"], taps[first.name + ".conv1"], taps[first.name + ".shortcut"], taps[first.name] = bev.clone(), b["c1"].clone(), b["ds"].clone(), x.clone()
+        for i, blk in enumerate(self.agent_blocks[1:], start=1):
+            out = b["x"][i % 2]                                         # (block i reads b["x"][(i - 1) % 2]: two buffers, as on the LiDAR path)
+            self._conv3x3(blk.conv1, x, n, mh, mw, b["c1"], blk.conv1.out_q)
+            if blk.down is not None:
+                self._conv1x1(blk.down, x, n, mh, mw, b["ds"], 1)
+                self._conv3x3(blk.conv2, b["c1"], n, mh, mw, out, blk.out_q, 2, b["ds"])
+            else:
+                self._conv3x3(blk.conv2, b["c1"], n, mh, mw, out, blk.out_q, 3, x, xq)
+            if taps is not None:
+                taps[blk.name + ".conv1"], taps[blk.name] = b["c1"].clone(), out.clone()
+            x, xq = out, blk.out_q
+        # one strided copy: the window both maps share (the conv entry writes whole maps only); the rest of enc_in keeps the code of 0.0
+        (top, bottom, left, right), (ct, cl) = center_crop_window(mh, mw, self.fh, self.fw)
+        dy, dx = max(top - ct, 0), max(left - cl, 0)                       # where the camera map's first kept cell lands in enc_in
+        sy, sx = max(ct - top, 0), max(cl - left, 0)                       # and which cell of the camera map that is
+        rows, cols = min(self.fh - dy, mh - sy), min(self.fw - dx, mw - sx)
+        b["enc_in"][:, 1 + dy:1 + dy + rows, 1 + dx:1 + dx + cols, :first.cout].copy_(x[:, 1 + sy:1 + sy + rows, 1 + sx:1 + sx + cols, :])
+        if taps is not None:
+            taps["enc_in"] = b["enc_in"].clone()
+        return b["enc_in"]
+
     def agent_backbone(self, n: int, taps: Optional[dict] = None):
         b = self._agent_ws(n)
         x, h, w, xq = b["canvas"], self.ny, self.nx, (self.pfn.d2, int(self.pfn.z2))
@@ -452,6 +552,9 @@ class DeployedPyramidModel(nn.Module):
         """codes u8 [levels, n, H*W] of ``n`` agents (heter_pyramid_collab_codebook_mc_encdec.py:33-121)."""
         if not self.has_codebook:
             raise L.Qv2xError("encode_features: this model has no codebook (no wire format); call forward")
+        if self.camera:
+            self.camera_backbone(self.images_to_bev(inputs, n), n, taps)
+            return self.encode_codes(n, out)
         canvas = self.pillars_to_canvas(inputs, n)
         if taps is not None:
             taps["canvas"] = canvas
@@ -487,8 +590,23 @@ class DeployedPyramidModel(nn.Module):
         self._gconv(blk.conv2, t1, n, h, w, lv["t2"])
         self._conv1x1(blk.conv3, lv["t2"], n, ho, wo, out, 2, blk.out_q, feats_f32)
 
-    def _fuse_level(self, lvl, lv, x, xq, n, h, w, lens, pairwise, ego, cat, c0):
-        """occupancy head + score, weighted_fuse of every scene, the level's deblock into the concat; returns the fp32 occupancy maps"""
+    def crop_masks(self, agents) -> Optional[List[torch.Tensor]]:
+        """per pyramid level f32 [n, h * w] of 0 / 1 for the agents' modalities (``camera_bev.crop_mask_statement``), or None when no agent is a
+        camera; built once per distinct modality tuple"""
+        agents = tuple(str(a) for a in agents)
+        if not any(a in self.cam_crop_info for a in agents):
+            return None
+        if agents not in self._masks:
+            masks, (h, w) = [], self.feature_shape
+            for st in self.p_strides:
+                h, w = (h - 1) // st + 1, (w - 1) // st + 1
+                masks.append(torch.from_numpy(crop_mask_statement(agents, self.cam_crop_info, h, w)).to(self.dev))
+            self._masks[agents] = masks
+        return self._masks[agents]
+
+    def _fuse_level(self, lvl, lv, x, xq, n, h, w, lens, pairwise, ego, cat, c0, score_masks=None):
+        """occupancy head + score (times the level's camera crop mask when given), weighted_fuse of every scene, the level's deblock into the
+        concat; returns the fp32 occupancy maps"""
         st = L.current_stream
         oc = self.occ[lvl]
         d = L.OccDesc()
@@ -496,6 +614,8 @@ class DeployedPyramidModel(nn.Module):
         d.scale, d.bias, d.out_delta, d.out_zp = oc.scale, oc.bias, oc.out_q[0], float(oc.out_q[1])
         L.check(self.lib.qv2x_occ_score_i8(C.byref(d), L.ptr(x), L.ptr(oc.w), L.ptr(oc.lut), L.ptr(lv["score"]), L.ptr(lv["occ_code"]), st()), oc.name)
         occ = oc.occ_lut[lv["occ_code"].long()].view(n, 1, h, w)
+        if score_masks is not None:
+            lv["score"].mul_(score_masks[lvl])                            # a masked score is exactly 0: the fuse kernels turn it into -inf
         start = 0
         for bi, na in enumerate(lens):
             fd = self._fuse_desc(na, h, w, pairwise.shape[1], ego)
@@ -515,7 +635,7 @@ class DeployedPyramidModel(nn.Module):
 
     @torch.no_grad()
     def decode_features(self, codes, agent_stride: int, level_stride: int, lens: List[int], pairwise: torch.Tensor, ego: int = 0,
-                        taps: Optional[dict] = None) -> dict:
+                        taps: Optional[dict] = None, score_masks=None) -> dict:
         """``codes``: pointer / tensor of u8 planes, agent a's level-l plane at ``a * agent_stride + l * level_stride``; ``lens`` agents per
         scene; ``pairwise`` f64 [B, L, L, 4, 4] (heter_pyramid_collab_codebook_mc_encdec.py:123-181)."""
         if not self.has_codebook:
@@ -526,9 +646,9 @@ class DeployedPyramidModel(nn.Module):
         cptr = codes if isinstance(codes, C.c_void_p) else L.ptr(codes)
         L.check(self.lib.qv2x_codebook_decode_f32(cptr, agent_stride, level_stride, n, hw, self.levels, self.kc, self.D, L.ptr(self.lut), L.ptr(self.lut_bias),
                                                   L.ptr(b["feats"]), L.current_stream()), "qv2x_codebook_decode_f32")
-        return self._pyramid_and_heads(None, None, b["feats"], lens, pairwise, ego, taps)
+        return self._pyramid_and_heads(None, None, b["feats"], lens, pairwise, ego, taps, score_masks)
 
-    def _pyramid_and_heads(self, x, xq, feats_f32, lens: List[int], pairwise: torch.Tensor, ego: int, taps: Optional[dict]) -> dict:
+    def _pyramid_and_heads(self, x, xq, feats_f32, lens: List[int], pairwise: torch.Tensor, ego: int, taps: Optional[dict], score_masks=None) -> dict:
         """The ResNeXt levels on every agent's map -- codes ``x`` with quantizer ``xq``, or the decoded fp32 map -- fusion, deblocks,
         shrink_conv and the heads."""
         n, nb = sum(lens), len(lens)
@@ -550,9 +670,9 @@ class DeployedPyramidModel(nn.Module):
                 main = torch.cuda.current_stream()
                 self._side.wait_stream(main)
                 with torch.cuda.stream(self._side):
-                    occ_maps.append(self._fuse_level(lvl, lv, x, xq, n, h, w, lens, pairwise, ego, b["cat"], c0))
+                    occ_maps.append(self._fuse_level(lvl, lv, x, xq, n, h, w, lens, pairwise, ego, b["cat"], c0, score_masks))
             else:
-                occ_maps.append(self._fuse_level(lvl, lv, x, xq, n, h, w, lens, pairwise, ego, b["cat"], c0))
+                occ_maps.append(self._fuse_level(lvl, lv, x, xq, n, h, w, lens, pairwise, ego, b["cat"], c0, score_masks))
             c0 += self.deblocks[lvl].cout
             if taps is not None:
                 torch.cuda.current_stream().wait_stream(self._side) if self.overlap_levels else None
@@ -599,9 +719,22 @@ class DeployedPyramidModel(nn.Module):
     def forward(self, data_dict: dict, taps: Optional[dict] = None) -> dict:
         agents = data_dict["agent_modality_list"]
         n_total = len(agents)
-        if any(str(a) != "m1" for a in agents):
-            raise NotImplementedError("deployed path: every agent is the LiDAR modality 'm1'")
+        mine = str(self.state.get("meta/modality", "m1")) if self.camera else "m1"
+        # (integer modality codes index the MODEL's modality_name_list, which a camera state carries: heter_pyramid_collab.py:143-150)
+        names = modality_names_of(agents, self.modality_names) if self.camera else [str(a) for a in agents]
+        if any(a != mine for a in names):
+            raise NotImplementedError(f"deployed path: every agent is this engine's modality {mine!r} (DeployedHeterPyramidModel mixes modalities)")
         pairwise, lens = scene_layout(data_dict, n_total)
+        if self.camera:
+            masks, inputs = self.crop_masks(names), data_dict["inputs_" + mine]
+            if not self.has_codebook:                                # camera_pyramid.yaml: the cropped codes go straight into the pyramid
+                x = self.camera_backbone(self.images_to_bev(inputs, n_total), n_total, taps)
+                return self._pyramid_and_heads(x, self.agent_q, None, lens, pairwise, 0, taps, masks)
+            codes = self.encode_features(inputs, n_total, taps)
+            hw = self.fh * self.fw
+            if taps is not None:
+                taps["codes"] = codes
+            return self.decode_features(codes, hw, n_total * hw, lens, pairwise, 0, taps, masks)
         if not self.has_codebook:                                    # heter_pyramid_collab_mc: the agents' codes go straight into the pyramid
             canvas = self.pillars_to_canvas(data_dict["inputs_m1"], n_total)
             if taps is not None:
@@ -661,6 +794,10 @@ class DeployedHeterPyramidModel(nn.Module):
                 raise ValueError(f"modality {m}: feature map {e.fh} x {e.fw} / codebook {e.levels} x {e.kc} x {e.D} differs from the ego modality's")
         self.dev = self.main.dev
         self._slots: Dict[tuple, Dict[str, torch.Tensor]] = {}
+        # the ego's engine masks every camera modality's scores: cam_crop_info under the model's modality names
+        self.main.cam_crop_info = {m: {f"crop_ratio_W_{m}": e.crop_ratio_w, f"crop_ratio_H_{m}": e.crop_ratio_h}
+                                   for m, e in self.engines.items() if e.camera}
+        self.main._masks = {}
 
     @torch.no_grad()
     def forward(self, data_dict: dict, taps: Optional[dict] = None) -> dict:
@@ -671,7 +808,7 @@ class DeployedHeterPyramidModel(nn.Module):
                                    lambda eng, inputs, k, mt: eng.encode_features(inputs, k, mt), taps)
         if taps is not None:
             taps["codes"] = enc.view(lv, n_total, hw)
-        return self.main.decode_features(enc, hw, n_total * hw, lens, pairwise, 0, taps)
+        return self.main.decode_features(enc, hw, n_total * hw, lens, pairwise, 0, taps, self.main.crop_masks(agents))
 
     forward_with_encdec = forward
 

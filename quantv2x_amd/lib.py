@@ -31,7 +31,7 @@ SYMBOLS = [
     "qv2x_eval_workspace_bytes", "qv2x_eval_tp_fp_f32", "qv2x_gt_boxes_f32",
     "qv2x_range_search_workspace_bytes", "qv2x_range_search_f32",
     "qv2x_lss_workspace_bytes", "qv2x_lss_plan_f32", "qv2x_lss_splat_f32",
-    "qv2x_cam_stem_f32", "qv2x_cam_heads_i8",
+    "qv2x_cam_stem_f32", "qv2x_cam_heads_i8", "qv2x_bev_entry_f32",
 ]
 WIRES = {"f32": 0, "u8": 1}     # QV2X_WIRE_F32, QV2X_WIRE_U8
 COMM_ID_BYTES = 128
@@ -147,6 +147,11 @@ class CamHeadsDesc(C.Structure):
                 ("depth_delta", C.c_float), ("depth_zp", C.c_float), ("feat_delta", C.c_float), ("feat_zp", C.c_float)]
 
 
+class BevEntryDesc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("stride", C.c_int32),
+                ("downsample", C.c_int32), ("reserved", C.c_int32), ("out_delta", C.c_float), ("out_zp", C.c_float)]
+
+
 class Qv2xError(RuntimeError):
     pass
 
@@ -237,6 +242,7 @@ def load() -> C.CDLL:
     lib.qv2x_lss_splat_f32.argtypes = [C.POINTER(LssDesc), vp, vp, C.c_int, vp, vp, vp]
     lib.qv2x_cam_stem_f32.argtypes = [C.POINTER(CamStemDesc), vp, vp, vp, vp, vp]
     lib.qv2x_cam_heads_i8.argtypes = [C.POINTER(CamHeadsDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.qv2x_bev_entry_f32.argtypes = [C.POINTER(BevEntryDesc), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.qv2x_postprocess_workspace_bytes.argtypes = [C.POINTER(PostprocessDesc)]
     lib.qv2x_postprocess_workspace_bytes.restype = C.c_int64
     lib.qv2x_postprocess_f32.argtypes = [C.POINTER(PostprocessDesc), vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp]

@@ -25,10 +25,38 @@ def weighted_fuse(x, score, record_len, affine_matrix, align_corners):
     return torch.stack(fused)
 
 
+def cam_crop_mask(occ_map, agent_modality_list, cam_crop_info):
+    """The camera agents' score mask of one level (``pyramid_fuse.py:126-160``): ones for every agent whose modality has no entry in
+    ``cam_crop_info``; for a camera agent ones inside the centred rectangle of its own range less two cells per side, zeros outside.  The
+    rectangle is taken with the reference's indexing, so a negative start wraps and an empty one zeroes the agent's whole map."""
+    from ..heter_pyramid_collab_mc import modality_name
+    names = [modality_name(x) for x in agent_modality_list]
+    mask = torch.ones_like(occ_map)
+    _, _, H, W = mask.shape
+    for m in cam_crop_info:
+        sel = torch.tensor([x == m for x in names], dtype=torch.bool)
+        crop_H = H / cam_crop_info[m][f"crop_ratio_H_{m}"] - 4          # "There may be unstable response values at the edges."
+        crop_W = W / cam_crop_info[m][f"crop_ratio_W_{m}"] - 4
+        start_h, end_h = int(H // 2 - crop_H // 2), int(H // 2 + crop_H // 2)
+        start_w, end_w = int(W // 2 - crop_W // 2), int(W // 2 + crop_W // 2)
+        mask[sel, :, start_h:end_h, start_w:end_w] = 0
+        mask[sel] = 1 - mask[sel]
+    return mask
+
+
+def level_score(occ_map, agent_modality_list, cam_crop_info, training):
+    """``sigmoid(occ) + 1e-4``, times the camera crop mask in eval mode when there are camera modalities (``pyramid_fuse.py:145-162``)"""
+    score = torch.sigmoid(occ_map) + 1e-4
+    if cam_crop_info and not training:
+        score = score * cam_crop_mask(occ_map, agent_modality_list, cam_crop_info)
+    return score
+
+
 class PyramidFusion(nn.Module):
     """``PyramidFusion`` (``pyramid_fuse.py:64-179``): a ``ResNetBEVBackbone`` whose ``resnet`` is ResNeXt (grouped ``Bottleneck``s,
     32 x 4d, expansion 1) when ``resnext`` is set, plus one 1x1 occupancy head per level (``single_head_{i}``).  ``forward_collab``:
-    multiscale features of every agent -> per level: occupancy map, ``score = sigmoid(occ) + 1e-4``, ``weighted_fuse`` -> deblocks."""
+    multiscale features of every agent -> per level: occupancy map, ``score = sigmoid(occ) + 1e-4`` (camera agents: masked to their own
+    range in eval mode, ``cam_crop_mask``), ``weighted_fuse`` -> deblocks."""
 
     def __init__(self, model_cfg, input_channels=64):
         from ..sub_modules.base_bev_backbone_resnet import ResNetBEVBackbone
@@ -62,14 +90,13 @@ class PyramidFusion(nn.Module):
         return self.decode_multiscale_feature(feats), occ
 
     def forward_collab(self, spatial_features, record_len, affine_matrix, agent_modality_list=None, cam_crop_info=None):
-        if cam_crop_info:
-            raise NotImplementedError("camera crop masks: LiDAR modalities only on this path")
         feats = self.get_multiscale_feature(spatial_features)
         fused, occ = [], []
         for i in range(self.num_levels):
             o = getattr(self, f"single_head_{i}")(feats[i])
             occ.append(o)
-            fused.append(weighted_fuse(feats[i], torch.sigmoid(o) + 1e-4, record_len, affine_matrix, self.align_corners))
+            score = level_score(o, agent_modality_list, cam_crop_info, self.training)
+            fused.append(weighted_fuse(feats[i], score, record_len, affine_matrix, self.align_corners))
         return self.decode_multiscale_feature(fused), occ
 
     def forward(self, spatial_features, record_len=None, affine_matrix=None, agent_modality_list=None, cam_crop_info=None):

@@ -3,7 +3,8 @@ forward ``:164-249``): per-modality encoder + ``ResNetBEVBackbone`` + ``AlignNet
 ``PyramidFusion`` (ResNeXt levels, occupancy-weighted fusion, deblocks) -> ``shrink_conv`` -> shared 1x1 heads.
 
 Same ``args`` schema, attribute names (``encoder_m1``, ``backbone_m1``, ``aligner_m1``, ``pyramid_backbone``, ``shrink_conv``,
-``cls_head`` ...), output dict and ``state_dict`` keys as the reference.  LiDAR modalities only."""
+``cls_head`` ...), output dict and ``state_dict`` keys as the reference.  LiDAR modalities, and camera modalities with the reference's
+crop ratios, centre crop / pad and ``cam_crop_info`` (``heter_pyramid_collab.py:68-77, :173-190``)."""
 import importlib
 from collections import Counter, OrderedDict
 
@@ -31,6 +32,16 @@ def modality_name(x) -> str:
     raise TypeError(f"Unexpected type for modality: {type(x)}")
 
 
+def center_crop(x, target_h: int, target_w: int):
+    """torchvision's ``CenterCrop((target_h, target_w))`` on [..., H, W], restated (``camera_bev.center_crop_window`` holds the arithmetic):
+    zero padding where the target is larger, then the crop"""
+    from ...camera_bev import center_crop_window
+    (top, bottom, left, right), (ct, cl) = center_crop_window(x.shape[-2], x.shape[-1], target_h, target_w)
+    if top or bottom or left or right:
+        x = torch.nn.functional.pad(x, (left, right, top, bottom))
+    return x[..., ct:ct + target_h, cl:cl + target_w]
+
+
 class HeterPyramidCollabMC(nn.Module):
     def __init__(self, args):
         super().__init__()
@@ -44,8 +55,8 @@ class HeterPyramidCollabMC(nn.Module):
         for name in self.modality_name_list:
             cfg = args[name]
             self.sensor_type_dict[name] = cfg['sensor_type']
-            if cfg['sensor_type'] != 'lidar':
-                raise NotImplementedError("only LiDAR modalities are on the accelerated path (SURVEY.md §2)")
+            if cfg['sensor_type'] not in ('lidar', 'camera'):
+                raise NotImplementedError(f"sensor_type {cfg['sensor_type']!r}: LiDAR and camera modalities are on the accelerated path")
             enc_cls = find_class(encoders, cfg['core_method'])
             if enc_cls is None:
                 raise NotImplementedError(f"encoder {cfg['core_method']!r} is outside the hot path")
@@ -53,6 +64,14 @@ class HeterPyramidCollabMC(nn.Module):
             setattr(self, f"depth_supervision_{name}", bool(cfg['encoder_args'].get("depth_supervision", False)))
             setattr(self, f"backbone_{name}", ResNetBEVBackbone(cfg['backbone_args']))
             setattr(self, f"aligner_{name}", AlignNet(cfg['aligner_args']))
+            if cfg['sensor_type'] == 'camera':                                           # heter_pyramid_collab.py:68-77
+                grid = cfg['camera_mask_args']['grid_conf']
+                setattr(self, f"crop_ratio_W_{name}", self.cav_range[3] / grid['xbound'][1])
+                setattr(self, f"crop_ratio_H_{name}", self.cav_range[4] / grid['ybound'][1])
+                setattr(self, f"xdist_{name}", grid['xbound'][1] - grid['xbound'][0])
+                setattr(self, f"ydist_{name}", grid['ybound'][1] - grid['ybound'][0])
+                self.cam_crop_info[name] = {f"crop_ratio_W_{name}": getattr(self, f"crop_ratio_W_{name}"),
+                                            f"crop_ratio_H_{name}": getattr(self, f"crop_ratio_H_{name}")}
 
         self.H = self.cav_range[4] - self.cav_range[1]
         self.W = self.cav_range[3] - self.cav_range[0]
@@ -91,8 +110,10 @@ class HeterPyramidCollabMC(nn.Module):
         return f"Model Memory Footprint: {total / (1024 ** 2):.2f} MB"
 
     # ---- forward in stages (the codebook subclasses and the deployed engine reuse them) ----
-    def encode_agents(self, data_dict):
-        """Per-agent BEV features in ``agent_modality_list`` order: [sum_N, C, H, W] (2x downsampled)."""
+    def encode_agents(self, data_dict, output_dict=None):
+        """Per-agent BEV features in ``agent_modality_list`` order: [sum_N, C, H, W] (2x downsampled).  A camera modality's map is centre
+        cropped or zero padded to the LiDAR range after its aligner (``heter_pyramid_collab.py:173-190``); with ``depth_supervision`` its
+        encoder's depth items go into ``output_dict``."""
         agents = [modality_name(x) for x in data_dict['agent_modality_list']]
         present = Counter(agents)
         per_mod = {}
@@ -100,7 +121,13 @@ class HeterPyramidCollabMC(nn.Module):
             if name in present:
                 f = getattr(self, f"encoder_{name}")(data_dict, name)
                 f = getattr(self, f"backbone_{name}")(f)
-                per_mod[name] = getattr(self, f"aligner_{name}")(f)
+                f = getattr(self, f"aligner_{name}")(f)
+                if self.sensor_type_dict[name] == 'camera':
+                    h, w = f.shape[-2:]
+                    f = center_crop(f, int(h * getattr(self, f"crop_ratio_H_{name}")), int(w * getattr(self, f"crop_ratio_W_{name}")))
+                    if getattr(self, f"depth_supervision_{name}") and output_dict is not None:
+                        output_dict[f"depth_items_{name}"] = getattr(self, f"encoder_{name}").depth_items
+                per_mod[name] = f
         taken = {name: 0 for name in self.modality_name_list}
         rows = []
         for name in agents:
@@ -123,5 +150,5 @@ class HeterPyramidCollabMC(nn.Module):
     def forward(self, data_dict):
         out = {'pyramid': 'collab'}
         affine = normalize_pairwise_tfm(data_dict['pairwise_t_matrix'], self.H, self.W, self.fake_voxel_size)
-        feats = self.transform_features(self.encode_agents(data_dict), out)
+        feats = self.transform_features(self.encode_agents(data_dict, out), out)
         return self.fuse_and_detect(feats, data_dict['record_len'], affine, data_dict['agent_modality_list'], out)

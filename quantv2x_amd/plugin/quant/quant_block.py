@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..models.fuse_modules.pyramid_fuse import PyramidFusion, weighted_fuse
+from ..models.fuse_modules.pyramid_fuse import PyramidFusion, level_score, weighted_fuse
 from ..models.heter_encoders import SECOND, LiftSplatShoot, PointPillar, pool_bev
 from ..models.sub_modules.base_bev_backbone import BaseBEVBackbone
 from ..models.sub_modules.base_bev_backbone_resnet import ResNetBEVBackbone
@@ -363,14 +363,13 @@ class QuantPyramidFusion(QuantResNetBEVBackbone):
         return self.decode_multiscale_feature(feats), occ
 
     def forward_collab(self, spatial_features, record_len, affine_matrix, agent_modality_list=None, cam_crop_info=None):
-        if cam_crop_info:
-            raise NotImplementedError("camera crop masks: LiDAR modalities only on this path")
         feats = self.get_multiscale_feature(spatial_features)
         fused, occ = [], []
         for i in range(self.num_levels):
             o = getattr(self, f"single_head_{i}")(feats[i])
             occ.append(o)
-            fused.append(weighted_fuse(feats[i], torch.sigmoid(o) + 1e-4, record_len, affine_matrix, self.align_corners))
+            score = level_score(o, agent_modality_list, cam_crop_info, self.training)
+            fused.append(weighted_fuse(feats[i], score, record_len, affine_matrix, self.align_corners))
         return self.decode_multiscale_feature(fused), occ
 
     def forward(self, spatial_features, record_len=None, affine_matrix=None, agent_modality_list=None, cam_crop_info=None):

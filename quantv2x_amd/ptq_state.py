@@ -12,6 +12,7 @@ used -- and collects exactly what the deployed integer path needs:
   <module>/a_delta, <module>/a_zp   f32 scalars of the output activation quantizer
   pfn/a2_delta, pfn/a2_zp           the extra quantizer of QuantPFNLayer (quant_block.py:619-621)
   codebook/...                      fp32 heads + codebooks (the codebook is left unquantized)
+  camera/...                        a camera modality's image encoder: ``export_camera_state``'s own dict (Pyramid models)
   meta/...                          geometry of the BEV grid
 
 ``save_ptq_state`` / ``load_ptq_state`` store it as one ``.npz``.
@@ -53,9 +54,16 @@ def _is_pyramid(model) -> bool:
     return hasattr(model, "pyramid_backbone")
 
 
+def _camera_prefixes(model):
+    """``encoder_<m>.`` of every camera modality: those modules are the camera encoder's own (``export_camera_state`` checks and exports them)"""
+    sensors = getattr(model, "sensor_type_dict", None) or {}
+    return tuple(f"encoder_{m}." for m, kind in sensors.items() if kind == "camera")
+
+
 def _residual_blocks(model):
-    """(name, block) of every quantized residual block (QuantBasicBlock / QuantBottleneck, quant_block.py:68-131)."""
-    return [(n, m) for n, m in model.named_modules() if type(m).__name__ in ("QuantBasicBlock", "QuantBottleneck")]
+    """(name, block) of every quantized residual block (QuantBasicBlock / QuantBottleneck, quant_block.py:68-131) outside the camera encoders."""
+    cam = _camera_prefixes(model)
+    return [(n, m) for n, m in model.named_modules() if type(m).__name__ in ("QuantBasicBlock", "QuantBottleneck") and not n.startswith(cam)]
 
 
 def _check_structure(model) -> None:
@@ -86,8 +94,11 @@ def _check_structure(model) -> None:
     if getattr(model, "compress", False) and (pyramid or getattr(model, "codebook", None) is not None):
         raise NotImplementedError("deployed path: the NaiveCompressor ('compressor' in the model args) is built for the baseline models "
                                   "without a codebook (the codebook models never call it, heter_baseline_collab_codebook.py:119-132)")
+    cam = _camera_prefixes(model)
+    if cam and not pyramid:
+        raise NotImplementedError("camera modalities deploy in the Pyramid models (heter_pyramid_collab*); the AttFuse baseline is LiDAR only")
     for name, m in model.named_modules():
-        if not _is_quant_module(m):
+        if not _is_quant_module(m) or name.startswith(cam):
             continue
         if type(getattr(m, "norm_function", None)).__name__ != "StraightThrough":
             raise NotImplementedError(f"{name}: an unfolded norm_function ({type(m.norm_function).__name__}); build the QuantModel "
@@ -150,6 +161,7 @@ def export_ptq_state(qt_model, modality: str = "m1") -> Dict[str, np.ndarray]:
     if modality != "m1":
         out["meta/modality"] = np.array(modality)                   # (m1 states keep the key set the golden export pins)
     names, src_of = [], {}
+    cam_prefixes = _camera_prefixes(model)
     modules = dict(model.named_modules())
     for src_name, m in modules.items():
         if not _is_quant_module(m):
@@ -157,6 +169,8 @@ def export_ptq_state(qt_model, modality: str = "m1") -> Dict[str, np.ndarray]:
         pm = _PER_MODALITY.match(src_name)
         if pm and pm.group(2) != modality:
             continue                                                # another modality's stack: in that modality's own state
+        if src_name.startswith(cam_prefixes):
+            continue                                                # the camera encoder: export_camera_state's own dict, below
         name = _PER_MODALITY.sub(lambda g: f"{g.group(1)}_m1{g.group(3)}", src_name) if pm else src_name
         out.update(_module_entries(name, m))
         names.append(name)
@@ -165,7 +179,24 @@ def export_ptq_state(qt_model, modality: str = "m1") -> Dict[str, np.ndarray]:
     out["meta/w_bits"] = np.array([int(modules[src_of[n]].weight_quantizer.n_bits) for n in names], dtype=np.int32)   # 8, or 2..7 (W4A8)
 
     enc = getattr(model, "encoder_" + modality)
-    if type(enc).__name__ == "QuantSECOND":                       # the sparse encoder in front of the same 2-D path
+    sensor = (getattr(model, "sensor_type_dict", None) or {}).get(modality, "lidar")
+    if sensor == "camera":
+        # the camera encoder's entries are export_camera_state's own dict under CAMERA_PREFIX (its refusals -- EfficientNet, the Voxel form,
+        # an unfolded BatchNorm -- included); the rest of the state is what the engine needs around it
+        out["meta/sensor_type"] = np.array("camera")
+        cam_state = export_camera_state(enc)
+        if bool(cam_state["meta/use_gt_depth"]):
+            raise NotImplementedError("deployed camera agents: use_gt_depth puts a measured depth in place of the depth head")
+        out.update({CAMERA_PREFIX + k: v for k, v in cam_state.items()})
+        nx = [int(round((b[1] - b[0]) / b[2])) for b in (enc.grid_conf["xbound"], enc.grid_conf["ybound"], enc.grid_conf["zbound"])]
+        out["meta/encoder"] = np.array("lift_splat_shoot")
+        out["meta/grid"] = np.array(nx, dtype=np.int64)                                      # (X, Y, Z) cells of the camera's BEV grid
+        out["meta/canvas_channels"] = np.int64(int(enc.camC) * nx[2])
+        out["meta/inplanes"] = np.int64(getattr(model, "backbone_" + modality).model_cfg.get("inplanes", 64))
+        out["meta/crop_ratio_H"] = np.float64(getattr(model, "crop_ratio_H_" + modality))
+        out["meta/crop_ratio_W"] = np.float64(getattr(model, "crop_ratio_W_" + modality))
+        out["meta/modality_names"] = np.array(list(model.modality_name_list))                # what integer modality codes index
+    elif type(enc).__name__ == "QuantSECOND":                       # the sparse encoder in front of the same 2-D path
         if pyramid:
             raise NotImplementedError("deployed Pyramid path: PointPillar agents")
         out.update(export_second_state(enc))
@@ -334,6 +365,7 @@ def export_second_state(enc) -> Dict[str, np.ndarray]:
     return out
 
 
+CAMERA_PREFIX = "camera/"                               # where a Pyramid state of a camera modality keeps export_camera_state's dict
 CAMERA_TRUNK = (("layer1", 3), ("layer2", 4))          # what CamEncode_Resnet101 keeps of torchvision's ResNet-101: layer1 and layer2
 
 
