@@ -95,7 +95,12 @@ int qv2x_voxelize_batch_f32(const float* const* points /* host */, const int32_t
  *   (d2, z2) the second quantizer after the ReLU; vox/off = voxel size and (voxel/2 + range_min), xyz.
  *   canvas: padded i8 BEV [N][ny+2][nx+2][64], already filled with (z2 - 128). 
  * Slots past voxel_num_points must hold zeros (the voxel generator's padding; the reference's mean over all slots
- * relies on it too): only the filled slots are read. */
+ * relies on it too): only the filled slots are read.
+ * A pillar is written if and only if 0 <= agent < N, 0 <= y < ny and 0 <= z + x < nx (at row y + 1, column z + x + 1 of the padded
+ * canvas); every other row -- the voxelizer's tail rows (-1, -1, -1, -1) among them -- writes nothing.  Every row that lands inside the
+ * canvas must have voxel_num_points >= 1: with 0 the reference's mean is 0 / 0, so that input is outside the contract (rows outside the
+ * canvas may hold 0).  A count above max_points divides the mean by the reported count and sums over max_points slots, as the
+ * reference does.  Two rows on one cell are outside the contract too: the order between waves is not defined. */
 typedef struct {
     float w[64 * 10];
     float b[64];

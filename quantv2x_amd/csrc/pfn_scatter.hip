@@ -2,7 +2,7 @@
 // One wavefront per FOUR pillars, lane = output channel (64).  HBM-bound: reads M * (512 + 16 + 4) B, writes 64 B
 // per pillar.  Every quantization step is monotone non-decreasing, so max over points commutes with it: the
 // kernel takes the max of the pre-quantization value and quantizes once (bit-identical to the per-point form
-// in oracle/qv2x_oracle.c:orc_pfn, verified by tests/test_hip_parity.py).
+// in oracle/qv2x_oracle.c:orc_pfn, verified by tests/test_hip_parity.py and, at the kernels' edges, tests/test_hip_pfn_cases.py).
 #include "common.h"
 
 namespace qv2x {
