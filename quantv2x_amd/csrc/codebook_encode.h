@@ -82,7 +82,14 @@ __device__ __forceinline__ int span_cell(const SpanPlan& p, const EncArgs& a, in
 
 // codebook_encode_wave.hip
 int encode_wave_launch(const EncArgs& a, hipStream_t st);      // rows [a.m_lo, a.m_hi): one wave per 32
-int encode_wave_list_launch(const EncArgs& a, int waves, hipStream_t st);   // the cells a.list[0 .. *a.list_count): persistent waves
-int encode_wave_span_launch(const EncArgs& a, int waves, hipStream_t st);   // the same on the six span lists, a tile ends at its last undecided level
+// the cells a.list[0 .. *a.list_count): persistent waves; `span`: the six span lists, a tile ends at its last undecided level
+int encode_wave_list_launch(const EncArgs& a, int waves, bool span, hipStream_t st);
+
+// codebook_encode.hip.  The descriptor rules every entry of the encode family shares (the 64-wide, candidate and collapsed entries too), in the
+// messages of the entry `me`: `d` and the entry's other pointers (`ptrs`: all of them there) not null; n, h, w positive; 1 .. max_levels levels;
+// seg_num 1 | 2 | 4 up to max_segs (0 = 1: a descriptor from before the field existed); dict_size a multiple of 32 (of 64 with more than one
+// segment) up to max_kc, seg_num * dict_size <= 512 (sixteen 32-code tiles of the extended codebook).
+// Returns the effective seg_num, or the error (QV2X_EINVAL) after fail().
+int encode_check(const char* me, const qv2x_encode_desc* d, bool ptrs, int max_levels, int max_segs, int max_kc);
 
 }  // namespace qv2x

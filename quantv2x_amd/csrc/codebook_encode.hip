@@ -11,10 +11,6 @@
 // [32w, 32w + 32) for all 64 rows; for the distance GEMM one 32 x 32 (rows x codes) tile.
 // The argmin runs on the accumulator registers: half-wave butterfly on (distance, index) with ties to the lower
 // index, then a 4-way combine across waves through LDS.
-#include <cstdlib>
-
-#include <atomic>
-
 #include "codebook_encode.h"
 
 namespace qv2x {
@@ -494,75 +490,49 @@ extern "C" int qv2x_codebook_c2_f32(const float* codebook, int kc, float* c2, vo
 
 extern "C" int64_t qv2x_codebook_level_floats(int kc) { return qv2x::level_floats(kc); }
 
-static int encode_launch(const qv2x_encode_desc* d, const int8_t* in, const float* in_f32, const float* const* level_weights, uint8_t* codes, void* stream,
-                         int form = 0);
-
-// the wave-per-32-cells form whatever the launch size (qv2x_codebook_encode_f32 takes it from three rounds of the chip on): same codes
-extern "C" int qv2x_codebook_encode_wave_f32(const qv2x_encode_desc* d, const int8_t* in, const float* in_f32, const float* const* level_weights,
-                                             uint8_t* codes, void* stream) {
-    if (!in && !in_f32) return qv2x::fail(QV2X_EINVAL, "qv2x_codebook_encode_wave_f32: null pointer");
-    return encode_launch(d, in_f32 ? (const int8_t*)in_f32 : in, in_f32, level_weights, codes, stream, 1);
+int qv2x::encode_check(const char* me, const qv2x_encode_desc* d, bool ptrs, int max_levels, int max_segs, int max_kc) {
+    if (!d || !ptrs) return fail(QV2X_EINVAL, "%s: null pointer", me);
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->levels < 1 || d->levels > max_levels)
+        return fail(QV2X_EINVAL, "%s: n, h, w must be positive, levels 1 .. %d (got %d x %d x %d, %d levels)", me, max_levels, d->n, d->h, d->w, d->levels);
+    const int segs = d->segs ? d->segs : 1;                            // (0: a descriptor from before the field existed)
+    if ((segs != 1 && segs != 2 && segs != 4) || segs > max_segs)
+        return fail(QV2X_EINVAL, "%s: seg_num must be 1, 2 or 4 and at most %d here (got %d)", me, max_segs, d->segs);
+    if (d->kc < 32 || d->kc > max_kc || d->kc % 32 || (segs > 1 && d->kc % 64) || segs * d->kc > 32 * ENC_MAX_TILES)
+        return fail(QV2X_EINVAL, "%s: dict_size must be a multiple of 32 up to %d (of 64 with seg_num > 1; seg_num * dict_size <= %d): "
+                                 "got dict_size %d, seg_num %d", me, max_kc, 32 * ENC_MAX_TILES, d->kc, segs);
+    return segs;
 }
 
-extern "C" int qv2x_codebook_encode_f32(const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
-                                        uint8_t* codes, void* stream) {
-    return encode_launch(d, in, nullptr, level_weights, codes, stream);
-}
-
-extern "C" int qv2x_codebook_encode_f32in(const qv2x_encode_desc* d, const float* in, const float* const* level_weights,
-                                          uint8_t* codes, void* stream) {
-    if (!in) return qv2x::fail(QV2X_EINVAL, "qv2x_codebook_encode_f32in: null pointer");
-    return encode_launch(d, (const int8_t*)in, in, level_weights, codes, stream);
+// The EncArgs of a checked descriptor, or QV2X_EALIGN: `in` and every level's blob are 16-byte aligned
+static int encode_args(const char* me, const qv2x_encode_desc* d, int segs, const int8_t* in, const float* in_f32, const float* const* level_weights,
+                       uint8_t* codes, qv2x::EncArgs& a) {
+    using namespace qv2x;
+    if ((uintptr_t)in & 15) return fail(QV2X_EALIGN, "%s: in must be 16-byte aligned", me);
+    a.in = in; a.in_f32 = in_f32; a.codes = codes; a.n = d->n; a.h = d->h; a.w = d->w; a.levels = d->levels; a.kc = d->kc;
+    a.segs = segs; a.ke = segs * d->kc;
+    a.ax = 128 - d->in_zx; a.dx = d->in_delta; a.M = d->n * d->h * d->w; a.m_lo = 0; a.m_hi = a.M;
+    for (int l = 0; l < 4; ++l) {
+        a.lvl[l] = l < d->levels ? level_weights[l] : nullptr;
+        if (l < d->levels && (!a.lvl[l] || ((uintptr_t)a.lvl[l] & 15))) return fail(QV2X_EALIGN, "%s: level %d weights null or unaligned", me, l);
+    }
+    return QV2X_OK;
 }
 
 // Stage 2 of the two-stage exact encode (encode_two_stage.py, codebook_encode_cand.hip): qv2x_codebook_encode_f32's arithmetic on the cells
 // `list[0 .. *list_count)` only -- the count lives on the DEVICE (the candidate stage wrote it), the launch is a fixed number of persistent
 // waves, so the pair of launches is capturable in a HIP graph.
-static int encode_listed(const bool span, const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
-                         const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream);
-
-extern "C" int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
-                                               const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream) {
-    return encode_listed(false, d, in, level_weights, list, list_count, codes, stream);
-}
-
-// The span form (include/qv2x.h): six lists by (first, last) undecided level, a tile of 32 listed cells ends at its last undecided level when
-// the chain has confirmed every stored candidate up to there.  Same split between persistent waves and workgroups, same fixed launches.
-extern "C" int qv2x_codebook_encode_span_f32(const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
-                                             const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream) {
-    if (d && d->levels > 3) return qv2x::fail(QV2X_EINVAL, "qv2x_codebook_encode_span_f32: up to three levels (the span lists have no class beyond level 2)");
-    return encode_listed(true, d, in, level_weights, list, list_count, codes, stream);
-}
-
-// (the messages name qv2x_codebook_encode_listed_f32 for both entries: the argument rules are its own)
-static int encode_listed(const bool span, const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
+static int encode_listed(const char* me, const bool span, const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
                          const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream) {
     using namespace qv2x;
-    if (!d ||!in || !level_weights || !codes || !list || !list_count) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: null pointer");
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->levels < 1 || d->levels > 4) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: bad shape");
-    const int segs = d->segs ? d->segs : 1;
-    if (segs != 1 && segs != 2) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: seg_num 1 or 2 (got %d)", d->segs);
-    if (d->kc < 32 || d->kc > 256 || d->kc % 32 || (segs > 1 && d->kc % 64) || segs * d->kc > 32 * ENC_MAX_TILES)
-        return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: dict_size must be a multiple of 32 up to 256 (of 64 with two segments): got %d x %d", segs, d->kc);
-    if ((uintptr_t)in & 15) return fail(QV2X_EALIGN, "qv2x_codebook_encode_listed_f32: in must be 16-byte aligned");
+    const int segs = encode_check(me, d, in && level_weights && codes && list && list_count, 4, 2, 256);
+    if (segs < 0) return segs;
     EncArgs a;
-    a.in = in; a.in_f32 = nullptr; a.codes = codes; a.n = d->n; a.h = d->h; a.w = d->w; a.levels = d->levels; a.kc = d->kc;
-    a.segs = segs; a.ke = segs * d->kc;
+    if (int rc = encode_args(me, d, segs, in, nullptr, level_weights, codes, a)) return rc;
     const bool ext = segs > 1 || a.ke > 128;                           // (as encode_launch: the workgroup form's general variant)
-    a.ax = 128 - d->in_zx; a.dx = d->in_delta; a.M = d->n * d->h * d->w; a.m_lo = 0; a.m_hi = a.M;
     a.list = list; a.list_count = list_count;
-    for (int l = 0; l < 4; ++l) {
-        a.lvl[l] = l < d->levels ? level_weights[l] : nullptr;
-        if (l < d->levels && (!a.lvl[l] || ((uintptr_t)a.lvl[l] & 15))) return fail(QV2X_EALIGN, "qv2x_codebook_encode_listed_f32: level %d weights null or unaligned", l);
-    }
-    int cus = 256, dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+    const int cus = cu_count();
     const int tiles = (a.M + 31) / 32;
-    int tail_knob = 0;
-#ifdef QV2X_DEV_KNOBS                                                  // dev builds only: the largest remainder (tiles) the workgroup form takes
-    static const int tail_env = getenv("QV2X_LIST_TAIL") ? atoi(getenv("QV2X_LIST_TAIL")) : 0;
-    tail_knob = tail_env;
-#endif
+    static const int tail_knob = dev_knob("QV2X_LIST_TAIL", 0);        // dev builds only: the largest remainder (tiles) the workgroup form takes
     a.list_slots = 4 * cus; a.list_tail_max = tail_knob > 0 ? tail_knob : 2 * cus;
     // whole rounds of the chip's wave slots as persistent waves, the remainder as workgroups: both launches have a fixed size, the split is
     // made on the device from the count (list_plan).  Launches of fewer than two rounds of tiles (one or two frames) are the workgroup form's
@@ -570,7 +540,7 @@ static int encode_listed(const bool span, const qv2x_encode_desc* d, const int8_
     // of a one-frame graph even when it finds nothing to do.
     const int grid_tail = 2 * cus;
     if (tiles + 3 >= 2 * a.list_slots) {
-        if (int rc = span ? encode_wave_span_launch(a, a.list_slots, (hipStream_t)stream) : encode_wave_list_launch(a, a.list_slots, (hipStream_t)stream)) return rc;
+        if (int rc = encode_wave_list_launch(a, a.list_slots, span, (hipStream_t)stream)) return rc;
     } else {
         a.list_slots = 1 << 30; a.list_tail_max = 1 << 30;
     }
@@ -578,50 +548,28 @@ static int encode_listed(const bool span, const qv2x_encode_desc* d, const int8_
     // slower: 145 against 97 us for one frame, 1164 against 940 us at the batch.  Every workgroup streams the same 2.7 MB of weights, and what
     // the launch waits for is that stream (~3-4 TB/s over the chip whatever the prefetch depth), not the matrix pipe:
     // tools/probes/codebook_encode_tail16_experiment.hip, profiles/r06_tail16_experiment.log)
+    const int grid = tiles < grid_tail ? tiles : grid_tail;
     if (span) {
-        if (ext) codebook_encode_span_tail_kernel<true><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
-        else codebook_encode_span_tail_kernel<false><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
-    } else if (ext) codebook_encode_list_tail_kernel<true><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
-    else codebook_encode_list_tail_kernel<false><<<tiles < grid_tail ? tiles : grid_tail, 512, 0, (hipStream_t)stream>>>(a);
-    return hip_check(hipGetLastError(), "qv2x_codebook_encode_listed_f32 launch");
+        if (ext) codebook_encode_span_tail_kernel<true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+        else codebook_encode_span_tail_kernel<false><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+    } else if (ext) codebook_encode_list_tail_kernel<true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+    else codebook_encode_list_tail_kernel<false><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+    return hip_check(hipGetLastError(), me);
 }
 
-static int encode_launch(const qv2x_encode_desc* d, const int8_t* in, const float* in_f32, const float* const* level_weights, uint8_t* codes, void* stream,
-                         int form) {
+// form 1: the wave form whatever the launch size
+static int encode_launch(const char* me, const qv2x_encode_desc* d, const int8_t* in, const float* in_f32, const float* const* level_weights,
+                         uint8_t* codes, void* stream, int form = 0) {
     using namespace qv2x;
-    if (!d || !in || !level_weights || !codes) return fail(QV2X_EINVAL, "qv2x_codebook_encode_f32: null pointer");
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->levels < 1 || d->levels > 4) return fail(QV2X_EINVAL, "qv2x_codebook_encode_f32: bad shape");
-    const int segs = d->segs ? d->segs : 1;                            // (0: a descriptor from before the field existed)
-    if (segs != 1 && segs != 2 && segs != 4) return fail(QV2X_EINVAL, "qv2x_codebook_encode_f32: seg_num must be 1, 2 or 4 (got %d)", d->segs);
-    if (d->kc < 32 || d->kc > 256 || d->kc % 32 || (segs > 1 && d->kc % 64) || segs * d->kc > 32 * ENC_MAX_TILES)
-        return fail(QV2X_EINVAL, "qv2x_codebook_encode_f32: dict_size must be a multiple of 32 up to 256 (of 64 with seg_num > 1; seg_num * dict_size <= %d): "
-                                 "got dict_size %d, seg_num %d", 32 * ENC_MAX_TILES, d->kc, segs);
-    if ((uintptr_t)in & 15) return fail(QV2X_EALIGN, "qv2x_codebook_encode_f32: in must be 16-byte aligned");
+    const int segs = encode_check(me, d, in && level_weights && codes, 4, 4, 256);
+    if (segs < 0) return segs;
     EncArgs a;
-    a.in = in; a.in_f32 = in_f32; a.codes = codes; a.n = d->n; a.h = d->h; a.w = d->w; a.levels = d->levels; a.kc = d->kc;
-    a.segs = segs; a.ke = segs * d->kc;
+    if (int rc = encode_args(me, d, segs, in, in_f32, level_weights, codes, a)) return rc;
     const bool ext = segs > 1 || a.ke > 128;                           // (the workgroup form's general variant: encode_rows<ER, true>)
-    a.ax = 128 - d->in_zx; a.dx = d->in_delta; a.M = d->n * d->h * d->w; a.m_lo = 0; a.m_hi = a.M;
-    for (int l = 0; l < 4; ++l) {
-        a.lvl[l] = l < d->levels ? level_weights[l] : nullptr;
-        if (l < d->levels && (!a.lvl[l] || ((uintptr_t)a.lvl[l] & 15))) return fail(QV2X_EALIGN, "qv2x_codebook_encode_f32: level %d weights null or unaligned", l);
-    }
-    int er_env = 0;
-#ifdef QV2X_DEV_KNOBS                                                  // dev builds only: 32 | 64 | 96 (mixed) rows per workgroup, anything else is refused
-    static const int er_knob = [] { const char* e = getenv("QV2X_ENC_ROWS"); return e ? atoi(e) : 0; }();
-    if (er_knob != 0 && er_knob != 32 && er_knob != 64 && er_knob != 96) return fail(QV2X_EINVAL, "QV2X_ENC_ROWS=%d: 32, 64 or 96", er_knob);
-    er_env = er_knob;
-#endif
-    static std::atomic<int> cus_of[64];                                // CU count per device, asked once (0 = not asked yet); relaxed atomics: every
-                                                                       // thread that finds 0 asks and stores the same value (reentrant per stream)
-    int cus = 256, dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        cus = cus_of[dev].load(std::memory_order_relaxed);
-        if (cus == 0) {
-            cus = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-            cus_of[dev].store(cus, std::memory_order_relaxed);
-        }
-    }
+    // dev builds only: 32 | 64 | 96 (mixed) rows per workgroup, anything else is refused
+    static const int er_env = dev_knob("QV2X_ENC_ROWS", 0);
+    if (er_env != 0 && er_env != 32 && er_env != 64 && er_env != 96) return fail(QV2X_EINVAL, "QV2X_ENC_ROWS=%d: 32, 64 or 96", er_env);
+    const int cus = cu_count();
     hipStream_t st = (hipStream_t)stream;
     if (form == 1) return encode_wave_launch(a, st);
     // The wave form (codebook_encode_wave.hip: a wave per 32 cells, one wave per SIMD) runs whole rounds of the chip's 4 x CUs wave slots
@@ -631,11 +579,8 @@ static int encode_launch(const qv2x_encode_desc* d, const int8_t* in, const floa
     // (profiles/r04_encode_by_frames.log).  Launches of less than one round keep the workgroup form's 64- / 32-row mix below.
     const int slots = 4 * cus, waves = (a.M + 31) / 32;
     const int rounds = waves / slots, rest = waves - rounds * slots;
-    int tail_max = 2 * cus;                                            // most workgroups a remainder may have
-#ifdef QV2X_DEV_KNOBS
-    static const int tail_knob = [] { const char* e = getenv("QV2X_ENC_TAIL"); return e ? atoi(e) : -1; }();   // 0: every remainder as waves
-    if (tail_knob >= 0) tail_max = tail_knob;
-#endif
+    static const int tail_knob = dev_knob("QV2X_ENC_TAIL", -1);        // dev builds only: most workgroups a remainder may have; 0: every remainder as waves
+    const int tail_max = tail_knob >= 0 ? tail_knob : 2 * cus;
     if (er_env == 0 && rounds >= 1) {
         if (rest == 0 || rest > tail_max) return encode_wave_launch(a, st);
         EncArgs main = a, tail = a;
@@ -644,7 +589,7 @@ static int encode_launch(const qv2x_encode_desc* d, const int8_t* in, const floa
         if (int rc = encode_wave_launch(main, st)) return rc;
         if (ext) codebook_encode_kernel<32, true><<<rest, 512, 0, st>>>(tail);
         else codebook_encode_kernel<32><<<rest, 512, 0, st>>>(tail);
-        return hip_check(hipGetLastError(), "qv2x_codebook_encode_f32 launch");
+        return hip_check(hipGetLastError(), me);
     }
     // Below one round of waves (a.M < 128 cells per CU): the mixed form when it has at least one full round of 64-row workgroups, else
     // 32-row workgroups.  (A whole launch of 64-row workgroups is a dev knob only since the split rule above: QV2X_ENC_ROWS=64.)
@@ -661,7 +606,37 @@ static int encode_launch(const qv2x_encode_desc* d, const int8_t* in, const floa
     } else {
         codebook_encode_kernel<32><<<(a.M + 31) / 32, 512, 0, st>>>(a);
     }
-    return hip_check(hipGetLastError(), "qv2x_codebook_encode_f32 launch");
+    return hip_check(hipGetLastError(), me);
+}
+
+// the wave-per-32-cells form whatever the launch size (qv2x_codebook_encode_f32 takes it from three rounds of the chip on): same codes
+extern "C" int qv2x_codebook_encode_wave_f32(const qv2x_encode_desc* d, const int8_t* in, const float* in_f32, const float* const* level_weights,
+                                             uint8_t* codes, void* stream) {
+    return encode_launch("qv2x_codebook_encode_wave_f32", d, in_f32 ? (const int8_t*)in_f32 : in, in_f32, level_weights, codes, stream, 1);
+}
+
+extern "C" int qv2x_codebook_encode_f32(const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
+                                        uint8_t* codes, void* stream) {
+    return encode_launch("qv2x_codebook_encode_f32", d, in, nullptr, level_weights, codes, stream);
+}
+
+extern "C" int qv2x_codebook_encode_f32in(const qv2x_encode_desc* d, const float* in, const float* const* level_weights,
+                                          uint8_t* codes, void* stream) {
+    return encode_launch("qv2x_codebook_encode_f32in", d, (const int8_t*)in, in, level_weights, codes, stream);
+}
+
+extern "C" int qv2x_codebook_encode_listed_f32(const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
+                                               const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream) {
+    return encode_listed("qv2x_codebook_encode_listed_f32", false, d, in, level_weights, list, list_count, codes, stream);
+}
+
+// The span form (include/qv2x.h): six lists by (first, last) undecided level, a tile of 32 listed cells ends at its last undecided level when
+// the chain has confirmed every stored candidate up to there.  Same split between persistent waves and workgroups, same fixed launches.
+extern "C" int qv2x_codebook_encode_span_f32(const qv2x_encode_desc* d, const int8_t* in, const float* const* level_weights,
+                                             const uint32_t* list, const uint32_t* list_count, uint8_t* codes, void* stream) {
+    const char* me = "qv2x_codebook_encode_span_f32";
+    if (d && d->levels > 3) return qv2x::fail(QV2X_EINVAL, "%s: up to three levels (the span lists have no class beyond level 2)", me);
+    return encode_listed(me, true, d, in, level_weights, list, list_count, codes, stream);
 }
 
 #ifdef QV2X_ENC_FINE

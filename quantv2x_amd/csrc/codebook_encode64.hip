@@ -6,7 +6,7 @@
 // each wave owns one 32 x 32 tile of the 64 x 64 GEMM outputs (row tile = wave >> 1, column tile = wave & 1) and two 32 x 32
 // (rows x codes) tiles of the distance GEMM.  x / z / q live in two LDS buffers (row stride 66 floats), the weights stream from L2
 // as [K/4][col][k0, k2, k1, k3] with the next four k-quads requested ahead of the current MFMAs; 34 KB of LDS: four workgroups per CU.
-#include "common.h"
+#include "codebook_encode.h"
 
 namespace qv2x {
 namespace {
@@ -474,24 +474,20 @@ extern "C" int qv2x_codebook64_c2_f32(const float* codebook, int kc, float* c2, 
     return hip_check(hipGetLastError(), "qv2x_codebook64_c2_f32 launch");
 }
 
-static int encode64_launch(const qv2x_encode_desc* d, int cin_total, const int8_t* in, const float* in_f32, const float* const* level_weights,
-                           uint8_t* codes, void* stream) {
+static int encode64_launch(const char* me, const qv2x_encode_desc* d, int cin_total, const int8_t* in, const float* in_f32,
+                           const float* const* level_weights, uint8_t* codes, void* stream) {
     using namespace qv2x;
-    if (!d || (!in && !in_f32) || !level_weights || !codes) return fail(QV2X_EINVAL, "qv2x_codebook_encode64_f32: null pointer");
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->levels < 1 || d->levels > 4) return fail(QV2X_EINVAL, "qv2x_codebook_encode64_f32: bad shape");
-    const int segs = d->segs ? d->segs : 1;
-    if ((segs != 1 && segs != 2 && segs != 4) || d->kc < 32 || d->kc > 256 || d->kc % 32 || (segs > 1 && d->kc % 64) || segs * d->kc > 32 * MAX_TILES)
-        return fail(QV2X_EINVAL, "qv2x_codebook_encode64_f32: seg_num 1 | 2 | 4, dict_size a multiple of 32 up to 256 (of 64 with seg_num > 1; "
-                                 "seg_num * dict_size <= %d): got dict_size %d, seg_num %d", 32 * MAX_TILES, d->kc, d->segs);
+    const int segs = encode_check(me, d, (in || in_f32) && level_weights && codes, 4, 4, 256);
+    if (segs < 0) return segs;
     if (cin_total < 64 || cin_total % 16 || ((uintptr_t)in & 15) || ((uintptr_t)in_f32 & 15))
-        return fail(QV2X_EALIGN, "qv2x_codebook_encode64_f32: >= 64 channels (%% 16), 16-byte aligned map");
+        return fail(QV2X_EALIGN, "%s: >= 64 channels (%% 16), 16-byte aligned map", me);
     Enc64Args a;
     a.in = in; a.in_f32 = in_f32; a.codes = codes; a.n = d->n; a.h = d->h; a.w = d->w; a.cin_total = cin_total; a.levels = d->levels; a.kc = d->kc;
     a.segs = segs; a.ke = segs * d->kc;
     a.ax = 128 - d->in_zx; a.dx = d->in_delta; a.M = d->n * d->h * d->w;
     for (int l = 0; l < 4; ++l) {
         a.lvl[l] = l < d->levels ? level_weights[l] : nullptr;
-        if (l < d->levels && (!a.lvl[l] || ((uintptr_t)a.lvl[l] & 15))) return fail(QV2X_EALIGN, "qv2x_codebook_encode64_f32: level %d weights null or unaligned", l);
+        if (l < d->levels && (!a.lvl[l] || ((uintptr_t)a.lvl[l] & 15))) return fail(QV2X_EALIGN, "%s: level %d weights null or unaligned", me, l);
     }
     // a wave per 32 cells from 2048 cells on (round 5: 172 -> see DESIGN.md 3 / profiles/r05_deconv_ps.log); below, the workgroup form
     if (a.M >= 2048) {
@@ -501,15 +497,15 @@ static int encode64_launch(const qv2x_encode_desc* d, int cin_total, const int8_
     } else {
         codebook_encode64_kernel<<<(a.M + ER - 1) / ER, 256, 0, (hipStream_t)stream>>>(a);
     }
-    return hip_check(hipGetLastError(), "qv2x_codebook_encode64_f32 launch");
+    return hip_check(hipGetLastError(), me);
 }
 
 extern "C" int qv2x_codebook_encode64_f32(const qv2x_encode_desc* d, int cin_total, const int8_t* in, const float* const* level_weights,
                                           uint8_t* codes, void* stream) {
-    return encode64_launch(d, cin_total, in, nullptr, level_weights, codes, stream);
+    return encode64_launch("qv2x_codebook_encode64_f32", d, cin_total, in, nullptr, level_weights, codes, stream);
 }
 
 extern "C" int qv2x_codebook_encode64_f32in(const qv2x_encode_desc* d, int cin_total, const float* in, const float* const* level_weights,
                                             uint8_t* codes, void* stream) {
-    return encode64_launch(d, cin_total, nullptr, in, level_weights, codes, stream);
+    return encode64_launch("qv2x_codebook_encode64_f32in", d, cin_total, nullptr, in, level_weights, codes, stream);
 }

@@ -34,7 +34,7 @@
 // two segments CT = 3 (96 cells share 1.15 MB); CT = 2 where the large tile would not reach every SIMD (one V2X-Real frame at (1, 128),
 // 275 waves of 128 cells on 1024 SIMDs: 51.9 us; of 64 cells 33.2; of 32 cells 40.9 -- the limbs are streamed per wave; four frames:
 // 106.6 / 96.2 / 100.7).  Registers and scratch: DESIGN.md §3.1, profiles/r08_candidate_kernel_resources.txt.
-#include "common.h"
+#include "codebook_encode.h"
 
 namespace qv2x {
 namespace {
@@ -284,13 +284,8 @@ void launch(const CandArgs& a, hipStream_t st) {
 template <int PACK, int MAX_SEGS, bool SPAN = false>
 int candidates(const char* me, const qv2x_encode_desc* d, const int8_t* in, const int8_t* g_limbs, const double* bias_packed, const int32_t* tables,
                const float* tau, uint8_t* codes, uint32_t* list, uint32_t* counters, void* stream) {
-    if (!d || !in || !g_limbs || !bias_packed || !tau || !codes || !list || !counters) return fail(QV2X_EINVAL, "%s: null pointer", me);
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->levels < 1 || d->levels > 3) return fail(QV2X_EINVAL, "%s: 1..3 levels", me);
-    const int segs = d->segs ? d->segs : 1;
-    if (segs < 1 || segs > MAX_SEGS) return fail(QV2X_EINVAL, "%s: seg_num 1 .. %d (got %d; the exact entry takes seg_num 1 | 2 | 4)", me, MAX_SEGS, d->segs);
-    // (seg_num <= 2 and dict_size <= 256 together are the header's seg_num * dict_size <= 512: no check of its own)
-    if (d->kc < 32 || d->kc > PACK || d->kc % 32 || (segs > 1 && d->kc % 64))
-        return fail(QV2X_EINVAL, "%s: dict_size a multiple of 32 up to %d (of 64 with two segments; got %d x %d)", me, PACK, segs, d->kc);
+    const int segs = encode_check(me, d, in && g_limbs && bias_packed && tau && codes && list && counters, 3, MAX_SEGS, PACK);
+    if (segs < 0) return segs;
     if (d->levels > 1 && !tables) return fail(QV2X_EINVAL, "%s: the residual levels need their tables", me);
     if (d->in_zx < 0 || d->in_zx > 255) return fail(QV2X_EINVAL, "%s: in_zx outside 0..255", me);
     if (((uintptr_t)in & 15) || ((uintptr_t)g_limbs & 15) || ((uintptr_t)tables & 15) || ((uintptr_t)bias_packed & 7))
@@ -305,8 +300,7 @@ int candidates(const char* me, const qv2x_encode_desc* d, const int8_t* in, cons
     a.delta = d->in_delta;
     hipStream_t st = (hipStream_t)stream;
     zero_counters_kernel<<<1, 64, 0, st>>>(counters, SPAN ? 8 : 4);
-    int dev = 0, cus = 256, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+    const int cus = cu_count();
     // the large tile (4 at one segment, 3 at two) from two rounds of its waves on every SIMD of the chip, the 64-cell wave below
     const bool large = a.M >= 4 * cus * 32 * (segs == 2 ? 3 : 4) * 2;
     if (segs == 1) large ? launch<4, 1, PACK, SPAN>(a, st) : launch<2, 1, PACK, SPAN>(a, st);

@@ -14,7 +14,7 @@
 // G and g), every wave runs 128 MFMAs with A converted from the bytes on the fly, scores land in LDS, then waves 0-7 run the argmin chain
 // (four cells per wave, two candidates per lane, lowest index wins ties; it adds the table rows of the codes already chosen) while waves
 // 8-11 bring in the next tile's bytes.  Always 12 waves: with fewer score columns the spare ones hold no slice of G.
-#include "common.h"
+#include "codebook_encode.h"
 
 namespace qv2x {
 namespace {
@@ -156,20 +156,17 @@ __global__ __launch_bounds__(768) void encode_collapsed_kernel(const CollArgs a)
 extern "C" int qv2x_codebook_encode_collapsed_f32(const qv2x_encode_desc* d, const int8_t* in, const float* g_packed, const float* bias,
                                                   const float* tables, uint8_t* codes, void* stream) {
     using namespace qv2x;
-    if (!d || !in || !g_packed || !bias || !codes) return fail(QV2X_EINVAL, "qv2x_codebook_encode_collapsed_f32: null pointer");
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->levels < 1 || d->levels > 3) return fail(QV2X_EINVAL, "qv2x_codebook_encode_collapsed_f32: 1..3 levels");
-    if (d->segs > 1) return fail(QV2X_EINVAL, "qv2x_codebook_encode_collapsed_f32: seg_num 1 only (the opt-in collapsed form; the exact entry takes seg_num 1 | 2 | 4)");
-    if (d->kc < 32 || d->kc > 128 || d->kc % 32) return fail(QV2X_EINVAL, "qv2x_codebook_encode_collapsed_f32: dict_size must be 32, 64, 96 or 128 (got %d)", d->kc);
-    if (d->levels > 1 && !tables) return fail(QV2X_EINVAL, "qv2x_codebook_encode_collapsed_f32: the residual levels need their tables");
-    if (((uintptr_t)in & 15) || ((uintptr_t)g_packed & 15)) return fail(QV2X_EALIGN, "qv2x_codebook_encode_collapsed_f32: 16-byte aligned pointers");
+    const char* me = "qv2x_codebook_encode_collapsed_f32";
+    if (int rc = encode_check(me, d, in && g_packed && bias && codes, 3, 1, 128); rc < 0) return rc;      // (seg_num 1 only: the opt-in collapsed form)
+    if (d->levels > 1 && !tables) return fail(QV2X_EINVAL, "%s: the residual levels need their tables", me);
+    if (((uintptr_t)in & 15) || ((uintptr_t)g_packed & 15)) return fail(QV2X_EALIGN, "%s: 16-byte aligned pointers", me);
     CollArgs a;
     a.in = in; a.gpack = g_packed; a.bias = bias; a.tables = tables; a.codes = codes;
     a.n = d->n; a.h = d->h; a.w = d->w; a.hw = d->h * d->w; a.R = d->n * a.hw; a.levels = d->levels; a.kc = d->kc; a.nct = d->levels * d->kc / 32;
     const int lds = 32 * RP + 32 * (a.nct * 32 + 1) * 4 + 12 * (128 - NR) * 64 * 4;
     if (int rc = hip_check(hipFuncSetAttribute((const void*)encode_collapsed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds), "collapsed encode LDS size")) return rc;
-    int dev = 0, cus = 256, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+    const int cus = cu_count();
     const int tiles = (a.R + 31) / 32;
     encode_collapsed_kernel<<<min(tiles, cus), 768, lds, (hipStream_t)stream>>>(a);
-    return hip_check(hipGetLastError(), "qv2x_codebook_encode_collapsed_f32 launch");
+    return hip_check(hipGetLastError(), me);
 }

@@ -450,21 +450,16 @@ int encode_wave_launch(const EncArgs& a, hipStream_t st) {
     return hip_check(hipGetLastError(), "qv2x_codebook_encode_f32 (wave form) launch");
 }
 
-
-// stage 2 of the two-stage encode: the listed cells, `waves` persistent single-wave workgroups (four per CU fill the chip)
-int encode_wave_list_launch(const EncArgs& a, int waves, hipStream_t st) {
-    if ((a.segs != 1 && a.segs != 2) || a.in_f32) return fail(QV2X_EINVAL, "qv2x_codebook_encode_listed_f32: seg_num 1 | 2, i8 rows");
-    if (a.segs == 2) codebook_encode_wave_kernel<false, 2, true><<<(unsigned)waves, 64, 0, st>>>(a);
-    else codebook_encode_wave_kernel<false, 1, true><<<(unsigned)waves, 64, 0, st>>>(a);
-    return hip_check(hipGetLastError(), "qv2x_codebook_encode_listed_f32 launch");
-}
-
-// the same on the six span lists (codebook_encode.h:span_plan): a tile ends at its cells' last undecided level
-int encode_wave_span_launch(const EncArgs& a, int waves, hipStream_t st) {
-    if ((a.segs != 1 && a.segs != 2) || a.in_f32) return fail(QV2X_EINVAL, "qv2x_codebook_encode_span_f32: seg_num 1 | 2, i8 rows");
-    if (a.segs == 2) codebook_encode_wave_kernel<false, 2, true, true><<<(unsigned)waves, 64, 0, st>>>(a);
+// stage 2 of the two-stage encode: the listed cells, `waves` persistent single-wave workgroups (four per CU fill the chip).  `span`: the six
+// span lists (codebook_encode.h:span_plan), a tile ends at its cells' last undecided level
+int encode_wave_list_launch(const EncArgs& a, int waves, bool span, hipStream_t st) {
+    if ((a.segs != 1 && a.segs != 2) || a.in_f32) return fail(QV2X_EINVAL, "listed encode (wave form): seg_num 1 | 2, i8 rows");
+    if (!span) {
+        if (a.segs == 2) codebook_encode_wave_kernel<false, 2, true><<<(unsigned)waves, 64, 0, st>>>(a);
+        else codebook_encode_wave_kernel<false, 1, true><<<(unsigned)waves, 64, 0, st>>>(a);
+    } else if (a.segs == 2) codebook_encode_wave_kernel<false, 2, true, true><<<(unsigned)waves, 64, 0, st>>>(a);
     else codebook_encode_wave_kernel<false, 1, true, true><<<(unsigned)waves, 64, 0, st>>>(a);
-    return hip_check(hipGetLastError(), "qv2x_codebook_encode_span_f32 launch");
+    return hip_check(hipGetLastError(), "listed encode (wave form) launch");
 }
 
 }  // namespace qv2x

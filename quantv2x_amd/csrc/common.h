@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#ifdef QV2X_DEV_KNOBS
+#include <cstdlib>
+#endif
 
 #include "../../include/qv2x.h"
 
@@ -9,6 +12,16 @@ namespace qv2x {
 
 int fail(int code, const char* fmt, ...);          // records the message for qv2x_last_error(), returns code
 int hip_check(hipError_t e, const char* what);      // 0 or -1000 - e
+int cu_count();                                     // CUs of the calling thread's current device, asked once per device (runtime.hip)
+
+// A development switch: the environment variable `name` as an int in builds with -DQV2X_DEV_KNOBS (tools/build_variant.py), `fallback` when it
+// is unset -- and in every other build, where the call folds to the constant.  A site keeps the value in a function-local `static const int`:
+// the variable is read once.
+#ifdef QV2X_DEV_KNOBS
+inline int dev_knob(const char* name, int fallback) { const char* e = getenv(name); return e ? atoi(e) : fallback; }
+#else
+constexpr int dev_knob(const char*, int fallback) { return fallback; }
+#endif
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));

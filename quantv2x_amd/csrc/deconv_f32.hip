@@ -10,8 +10,6 @@
 // LDS stage -- instead of sixteen 1-byte global stores per lane.
 #include "common.h"
 
-#include <cstdlib>
-
 namespace qv2x {
 
 struct DeconvArgs {
@@ -435,12 +433,7 @@ extern "C" int qv2x_deconv_i8(const qv2x_deconv_desc* d, const int8_t* in, const
     if (int rc = deconv_args(d, in, w, bias, out, "qv2x_deconv_i8", a)) return rc;
     // 32 x 32 wave tiles: 4416 tiles of 3.9 us on 1024 SIMDs at the 25 x 88 level balance better than 2208 tiles of 7.8 us
     // (13.7 / 21.4 / 36.4 us against 15.4 / 23.7 / 39.5 us for the three deblocks)
-#ifdef QV2X_DEV_KNOBS                                                  // dev build only: column tiles per wave
-    static const char* ntenv = getenv("QV2X_DECONV_NT");
-    const int nt = ntenv ? atoi(ntenv) : 1;
-#else
-    const int nt = 1;
-#endif
+    static const int nt = dev_knob("QV2X_DECONV_NT", 1);               // dev builds only: column tiles per wave
     const int tiles = ((a.M + 31) / 32) * (a.ncols / (32 * nt));
     if (nt == 1) deconv_f32_kernel<1><<<(tiles + 3) / 4, 256, 0, (hipStream_t)stream>>>(a);
     else deconv_f32_kernel<2><<<(tiles + 3) / 4, 256, 0, (hipStream_t)stream>>>(a);
@@ -469,19 +462,15 @@ extern "C" int qv2x_deconv_i8_batch(const qv2x_deconv_desc* descs, int n, const 
     // of 8 pairs - / 107 / 157 / 272 / 980)
     bool ps = true;
     for (int i = 0; i < n; ++i) ps = ps && ps_takes(b.a[i]);
-#ifdef QV2X_DEV_KNOBS
-    static const char* psenv = getenv("QV2X_DECONV_PS");
-    if (psenv && atoi(psenv) == 0) ps = false;
-#endif
+    static const int ps_knob = dev_knob("QV2X_DECONV_PS", 1);          // dev builds only: 0 = the tiles below at every shape
+    if (ps_knob == 0) ps = false;
     if (ps) {
         for (int i = 1; i < n; ++i)                                     // falling Cin (n <= 4: insertion sort)
             for (int j = i; j > 0 && b.a[j].cin > b.a[j - 1].cin; --j) { const DeconvArgs t = b.a[j]; b.a[j] = b.a[j - 1]; b.a[j - 1] = t; }
         int cap = 8, total = ps_plan(b, n, cap);
-#ifdef QV2X_DEV_KNOBS
-        static const char* npenv = getenv("QV2X_DECONV_NP");
-        if (npenv) { cap = atoi(npenv); total = ps_plan(b, n, cap); } else
-#endif
-        while (cap > 1 && total < 2560) total = ps_plan(b, n, cap >>= 1);
+        static const int np_knob = dev_knob("QV2X_DECONV_NP", -1);     // dev builds only: this cap (0 included) whatever the rule below finds
+        if (np_knob >= 0) total = ps_plan(b, n, np_knob);
+        else while (cap > 1 && total < 2560) total = ps_plan(b, n, cap >>= 1);
         b.n = n;
         deconv_ps_batch_kernel<false><<<dim3((total + 3) / 4), 256, 0, (hipStream_t)stream>>>(b);
         return hip_check(hipGetLastError(), "qv2x_deconv_i8_batch launch");

@@ -6,8 +6,6 @@
 //   affine_grid(theta, align_corners=False): x_j = (2j + 1)/W - 1, grid = theta . [x, y, 1]  (float64 theta ->
 //   float64 grid, cast to fp32 as the reference's `.to(src)` does), grid_sample bilinear / zeros.
 // Attention (fusion_in_one.py:41-45, 145-147): score_j = <f_0, f_j> / sqrt(C); softmax; out = sum_j p_j f_j.
-#include <cstdlib>
-
 #include "fuse_att.h"
 
 namespace qv2x {
@@ -123,11 +121,7 @@ static int fuse_att_batch_launch(const char* who, const qv2x_fuse_desc* d, int n
     // one tap per cell and are not bound by the table rows.
     // Three code planes and scenes of 2+ agents: the form with batched round trips (fuse_cell_b3; 88 against 105 us per scene of eight
     // V2X-Real agents, profiles/r05_fuse_by_agents.log).  QV2X_FUSE_MODE=0 (dev A/B switch, tools/bench_fuse.py): the round-4 walk.
-    int mode_env = -1;
-#ifdef QV2X_DEV_KNOBS
-    static const int mode_knob = [] { const char* e = getenv("QV2X_FUSE_MODE"); return e ? atoi(e) : -1; }();
-    mode_env = mode_knob;
-#endif
+    static const int mode_env = dev_knob("QV2X_FUSE_MODE", -1);
     const bool b3 = !feats && a.levels == 3 && most > 1 && mode_env != 0;   // (single-agent scenes: one tap per cell, nothing to batch)
     const dim3 grid((a.n_cells + 3) / 4, n_scenes);
     if (b3) {

@@ -1,4 +1,5 @@
 // Error plumbing + trivial entry points of the C ABI.
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 
@@ -18,6 +19,19 @@ int fail(int code, const char* fmt, ...) {
 int hip_check(hipError_t e, const char* what) {
     if (e == hipSuccess) return QV2X_OK;
     return fail(-1000 - (int)e, "%s: %s", what, hipGetErrorString(e));
+}
+
+// Cached per device id (0 = not asked yet); relaxed atomics: every thread that finds 0 asks and stores the same value.  A device id beyond
+// the array is asked every time; a failed query answers 256 (the MI355X) and is not cached.
+int cu_count() {
+    static std::atomic<int> cus_of[64];
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    const bool cached = dev >= 0 && dev < 64;
+    if (cached && (v = cus_of[dev].load(std::memory_order_relaxed)) != 0) return v;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
+    if (cached) cus_of[dev].store(v, std::memory_order_relaxed);
+    return v;
 }
 
 // 16 bytes per thread, grid-stride: a 9 MB canvas clears in ~2.5 us (the hipMemsetAsync node took 5.3 us in the graph)
