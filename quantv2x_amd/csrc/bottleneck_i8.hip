@@ -10,7 +10,8 @@
 //      (`out += residual`), ReLU, the block's quantizer, 16-byte stores through an LDS stage
 // Integer arithmetic, constants and results are those of the three separate kernels (tests/test_hip_pyramid_blocks.py::test_bottleneck holds
 // this launch to the oracle and to the three launches on random blocks with four different non-zero zero points).
-#include "common.h"
+#include "conv_host.h"
+#include "conv_i8_dev.h"
 
 namespace qv2x {
 namespace {
@@ -37,7 +38,7 @@ __global__ __launch_bounds__(256) void bottleneck_i8_kernel(const BnArgs a) {
     int8_t* t2 = smem + HP * P1;                        // [TH * 32][P1]
     int8_t* stage = t2 + TH * 32 * P1;                  // [4 waves][32][SP]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
-    const int tiles_x = (a.w + TW - 1) / TW, tiles_y = (a.h + TH - 1) / TH;
+    const int tiles_x = (a.w + TW - 1) / TW, tiles_y = (a.h + TH - 1) / TH;       // (tiles() here moved the kernel's instructions)
     const int img = blockIdx.x / (tiles_x * tiles_y), trem = blockIdx.x - img * (tiles_x * tiles_y);
     const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
     const int planes = a.cin;
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(256) void bottleneck_i8_kernel(const BnArgs a) {
             const int hp = pt * 32 + l31;
             const int hy = hp / HPW, hx = hp - hy * HPW;
             const int yc = min(max(y0 - 1 + hy, -1), a.h), xc = min(max(x0 - 1 + hx, -1), a.w);      // stay inside the padded tensor
-            const int8_t* src = a.x + ((size_t)(img * (a.h + 2) + yc + 1) * (a.w + 2) + xc + 1) * a.cin + 16 * half;
+            const int8_t* src = a.x + QV2X_BEV_PIXEL(size_t, img, yc, xc, a.h, a.w) * a.cin + 16 * half;
 #pragma unroll
             for (int ks = 0; ks < KS1; ++ks) dst[ks] = *(const v4i*)(src + 32 * ks);
         };
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(256) void bottleneck_i8_kernel(const BnArgs a) {
             const int tot = xs + __shfl_xor(xs, 32);
             const int y = y0 + ty, x = x0 + l31;
             const bool valid = y < a.h && x < a.w;
-            const size_t pix = (size_t)(img * (a.h + 2) + min(y, a.h - 1) + 1) * (a.w + 2) + min(x, a.w - 1) + 1;
+            const size_t pix = QV2X_BEV_PIXEL(size_t, img, min(y, a.h - 1), min(x, a.w - 1), a.h, a.w);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int ch = nt * 32 + 8 * g + 4 * half;
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(256) void bottleneck_i8_kernel(const BnArgs a) {
             {   // the row's 32 pixels x 32 bytes leave as 16-byte stores: pixel lane >> 1, piece lane & 1
                 const int xo = x0 + (lane >> 1);
                 if (y < a.h && xo < a.w)
-                    *(v4i*)(a.out + ((size_t)(img * (a.h + 2) + y + 1) * (a.w + 2) + xo + 1) * planes + nt * 32 + (lane & 1) * 16) =
+                    *(v4i*)(a.out + QV2X_BEV_PIXEL(size_t, img, y, xo, a.h, a.w) * planes + nt * 32 + (lane & 1) * 16) =
                         *(const v4i*)(st + (lane >> 1) * SP + (lane & 1) * 16);
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -207,8 +208,7 @@ int launch_bn(const BnArgs& a, hipStream_t st) {
     // > 64 KB of dynamic LDS needs the attribute; set on every call (a host-side driver call, no process-global "done" flag to go stale
     // on a second device; not part of a captured graph)
     if (int rc = hip_check(hipFuncSetAttribute((const void*)bottleneck_i8_kernel<KS1, NT1>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), "bottleneck LDS size")) return rc;
-    const int tiles = a.n * ((a.h + TH - 1) / TH) * ((a.w + TW - 1) / TW);
-    bottleneck_i8_kernel<KS1, NT1><<<tiles, 256, bytes, st>>>(a);
+    bottleneck_i8_kernel<KS1, NT1><<<a.n * tiles(a.h, TH) * tiles(a.w, TW), 256, bytes, st>>>(a);
     return hip_check(hipGetLastError(), "qv2x_bottleneck_i8 launch");
 }
 
@@ -219,15 +219,14 @@ extern "C" int qv2x_bottleneck_i8(const qv2x_bottleneck_desc* d, const int8_t* x
                                   const float* const* scale, const int32_t* const* corr, const int32_t* const* aw, const float* const* bias,
                                   int8_t* out, void* stream) {
     using namespace qv2x;
-    if (!d || !x || !w || !scale || !corr || !aw || !bias || !out) return fail(QV2X_EINVAL, "qv2x_bottleneck_i8: null pointer");
+    if (any_null(d, x, w, scale, corr, aw, bias, out)) return fail(QV2X_EINVAL, "qv2x_bottleneck_i8: null pointer");
     for (int i = 0; i < 3; ++i)
-        if (!w[i] || !scale[i] || !corr[i] || !aw[i] || !bias[i] || ((uintptr_t)w[i] & 15) || ((uintptr_t)scale[i] & 15) || ((uintptr_t)corr[i] & 15) ||
-            ((uintptr_t)aw[i] & 15) || ((uintptr_t)bias[i] & 15)) return fail(QV2X_EALIGN, "qv2x_bottleneck_i8: layer %d constants null or not 16-byte aligned", i);
+        if (any_null(w[i], scale[i], corr[i], aw[i], bias[i]) || misaligned16(w[i], scale[i], corr[i], aw[i], bias[i])) return fail(QV2X_EALIGN, "qv2x_bottleneck_i8: layer %d constants null or not 16-byte aligned", i);
     if (d->n <= 0 || d->h <= 0 || d->w <= 0) return fail(QV2X_EINVAL, "qv2x_bottleneck_i8: bad shape");
     if (d->width != 2 * d->planes || (d->planes != 64 && d->planes != 128 && d->planes != 256) || (d->cg != 4 && d->cg != 8 && d->cg != 16))
         return fail(QV2X_EINVAL, "qv2x_bottleneck_i8: planes 64 | 128 | 256, width = 2 x planes, 4 | 8 | 16 channels per group");
     if (!(d->delta1 > 0.0f) || !(d->delta2 > 0.0f) || !(d->out_delta > 0.0f)) return fail(QV2X_EINVAL, "qv2x_bottleneck_i8: quantizer steps must be positive");
-    if (((uintptr_t)x & 15) || ((uintptr_t)out & 15)) return fail(QV2X_EALIGN, "qv2x_bottleneck_i8: 16-byte aligned maps");
+    if (misaligned16(x, out)) return fail(QV2X_EALIGN, "qv2x_bottleneck_i8: 16-byte aligned maps");
     BnArgs a;
     a.x = x; a.out = out;
     a.w1 = w[0]; a.sc1 = scale[0]; a.cr1 = corr[0]; a.aw1 = aw[0]; a.bs1 = bias[0];

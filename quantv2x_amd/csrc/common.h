@@ -23,6 +23,10 @@ inline int dev_knob(const char* name, int fallback) { const char* e = getenv(nam
 constexpr int dev_knob(const char*, int fallback) { return fallback; }
 #endif
 
+// the argument checks every entry starts with (host): is one of the pointers null / not 16-byte aligned (a null pointer counts as aligned)
+template <class... P> bool any_null(const P*... p) { return (... || !p); }
+template <class... P> bool misaligned16(const P*... p) { return (... || ((uintptr_t)p & 15)); }
+
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef float v4f __attribute__((ext_vector_type(4)));

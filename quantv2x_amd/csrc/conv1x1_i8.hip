@@ -8,7 +8,8 @@
 // per-lane: the zero-point correction uses the lane's own window sum, four results requantize at a time (q_pack4) and the end of a
 // residual block -- out = quant(relu(conv3(x) + shortcut)) -- is fused: the shortcut comes in as fp32 (the strided 1x1 branch, or the
 // decoded feature in front of the first block) or as the block input's codes, dequantized in the epilogue.
-#include "common.h"
+#include "conv_host.h"
+#include "conv_i8_dev.h"
 
 namespace qv2x {
 namespace {
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(256) void conv1x1_i8_kernel(const C1Args a) {
         const int mm = min(tile * 32 + l31, a.M - 1);
         const int img = mm / (a.ho * a.wo), rem = mm - img * (a.ho * a.wo);
         const int yo = rem / a.wo, xo = rem - yo * a.wo;
-        const int8_t* src = a.in + ((size_t)(img * (a.h + 2) + yo * a.stride + 1) * (a.wd + 2) + xo * a.stride + 1) * a.cin + 16 * half;
+        const int8_t* src = a.in + QV2X_BEV_PIXEL(size_t, img, yo * a.stride, xo * a.stride, a.h, a.wd) * a.cin + 16 * half;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) dst[ks] = *(const v4i*)(src + 32 * ks);
     };
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void conv1x1_i8_kernel(const C1Args a) {
         const int mm = valid ? m : a.M - 1;
         const int img = mm / (a.ho * a.wo), rem = mm - img * (a.ho * a.wo);
         const int yo = rem / a.wo, xo = rem - yo * a.wo;
-        const int opix = (img * (a.ho + 2) + yo + 1) * (a.wo + 2) + xo + 1;       // padded output pixel
+        const int opix = QV2X_BEV_PIXEL(int, img, yo, xo, a.ho, a.wo);                 // padded output pixel
         v4f rf[2][4];                                               // the shortcut, requested ahead of the MFMAs
         int rw[2][4];
         if (MODE == 2 && valid) {
@@ -90,8 +91,7 @@ __global__ __launch_bounds__(256) void conv1x1_i8_kernel(const C1Args a) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const v4i fa0 = *(const v4i*)(wl + ks * 1024 + lane * 16), fa1 = *(const v4i*)(wl + (KS + ks) * 1024 + lane * 16);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) xs = __builtin_amdgcn_sdot4(fb[ks][q], 0x01010101, xs, false);
+            xs = sum16(fb[ks], xs);
             acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa0, fb[ks], acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa1, fb[ks], acc[1], 0, 0, 0);
         }
@@ -162,17 +162,16 @@ static void launch_c1(const C1Args& a, dim3 grid, hipStream_t st) {
 extern "C" int qv2x_conv1x1_i8(const qv2x_conv1x1_desc* d, const int8_t* in, const int8_t* w_frag, const float* scale, const int32_t* corr,
                                const int32_t* aw, const float* bias, const void* res, void* out, void* stream) {
     using namespace qv2x;
-    if (!d || !in || !w_frag || !scale || !corr || !aw || !bias || !out) return fail(QV2X_EINVAL, "qv2x_conv1x1_i8: null pointer");
+    if (any_null(d, in, w_frag, scale, corr, aw, bias, out)) return fail(QV2X_EINVAL, "qv2x_conv1x1_i8: null pointer");
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || (d->stride != 1 && d->stride != 2)) return fail(QV2X_EINVAL, "qv2x_conv1x1_i8: bad shape / stride");
     if ((d->cin != 64 && d->cin != 128 && d->cin != 256 && d->cin != 512) || d->cout % 64) return fail(QV2X_EALIGN, "qv2x_conv1x1_i8: cin 64 | 128 | 256 | 512, cout %% 64");
     if (d->mode < 0 || d->mode > 3) return fail(QV2X_EINVAL, "qv2x_conv1x1_i8: mode 0..3");
     if ((d->mode >= 2) && !res) return fail(QV2X_EINVAL, "qv2x_conv1x1_i8: mode %d needs the shortcut", d->mode);
-    if (((uintptr_t)in & 15) || ((uintptr_t)w_frag & 15) || ((uintptr_t)out & 15) || ((uintptr_t)res & 15) || ((uintptr_t)scale & 15) ||
-        ((uintptr_t)corr & 15) || ((uintptr_t)aw & 15) || ((uintptr_t)bias & 15)) return fail(QV2X_EALIGN, "qv2x_conv1x1_i8: 16-byte aligned pointers");
+    if (misaligned16(in, w_frag, out, res, scale, corr, aw, bias)) return fail(QV2X_EALIGN, "qv2x_conv1x1_i8: 16-byte aligned pointers");
     C1Args a;
     a.in = in; a.w = w_frag; a.scale = scale; a.corr = corr; a.aw = aw; a.bias = bias; a.res = res; a.out = out;
     a.n = d->n; a.h = d->h; a.wd = d->w; a.cin = d->cin; a.cout = d->cout; a.stride = d->stride;
-    a.ho = (d->h - 1) / d->stride + 1; a.wo = (d->w - 1) / d->stride + 1; a.M = d->n * a.ho * a.wo;
+    a.ho = conv_out(d->h, d->stride); a.wo = conv_out(d->w, d->stride); a.M = d->n * a.ho * a.wo;
     a.relu = d->relu; a.out_delta = d->out_delta; a.out_zp = d->out_zp; a.res_ax = 128 - d->res_zx; a.res_delta = d->res_delta;
     a.out_ctotal = d->mode == 1 ? d->cout : d->out_ctotal; a.out_c0 = d->mode == 1 ? 0 : d->out_c0;
     if (d->mode != 1) {
@@ -180,10 +179,10 @@ extern "C" int qv2x_conv1x1_i8(const qv2x_conv1x1_desc* d, const int8_t* in, con
         if (d->out_ctotal % 16 || d->out_c0 % 16 || d->out_ctotal < d->out_c0 + d->cout) return fail(QV2X_EALIGN, "qv2x_conv1x1_i8: out channel window (%% 16)");
     }
     // 32-pixel tiles per wave: as many as still leave two workgroups per CU
-    const int tiles = (a.M + 31) / 32, slices = a.cout / 64;
+    const int ntiles = tiles(a.M, 32), slices = a.cout / 64;
     a.tpw = 1;
-    while (a.tpw < 8 && (long long)((tiles + 8 * a.tpw - 1) / (8 * a.tpw)) * slices >= 512) a.tpw *= 2;
-    dim3 grid((tiles + 4 * a.tpw - 1) / (4 * a.tpw), slices);
+    while (a.tpw < 8 && (long long)tiles(ntiles, 8 * a.tpw) * slices >= 512) a.tpw *= 2;
+    dim3 grid(tiles(ntiles, 4 * a.tpw), slices);
     hipStream_t st = (hipStream_t)stream;
     switch (d->mode) {
         case 0: launch_c1<0>(a, grid, st); break;

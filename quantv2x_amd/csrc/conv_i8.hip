@@ -19,7 +19,8 @@
 // Wide stride-1 layers (cout % 256 == 0) have their own kernel and weight layout: conv_i8_wide.hip.
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_host.h"
+#include "conv_i8_dev.h"
 
 namespace qv2x {
 
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_i8_dma_kernel(const ConvArg
         if (m < a.M) {
             const int img = m / (a.ho * a.wo), rem = m - img * (a.ho * a.wo);
             const int yo = rem / a.wo, xo = rem - yo * a.wo;
-            off = (img * (a.ho + 2) + yo + 1) * (a.wo + 2) + xo + 1;
+            off = QV2X_BEV_PIXEL(int, img, yo, xo, a.ho, a.wo);
         }
         rowoff[tid] = off;
     }
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_i8_dma_kernel(const ConvArg
 
 template <int BM, int BN, int WM, int WN, int BK, bool MULTI, int S, int MINW, int EPI = 0>
 static int launch_dma(const ConvArgs& a, hipStream_t st) {
-    dim3 grid((a.M + BM - 1) / BM, a.cout / BN);
+    dim3 grid(tiles(a.M, BM), a.cout / BN);
     conv3x3_i8_dma_kernel<BM, BN, WM, WN, BK, MULTI, S, MINW, EPI><<<grid, 256, 0, st>>>(a);
     return hip_check(hipGetLastError(), "qv2x_conv3x3_i8 launch");
 }
@@ -344,31 +345,27 @@ static int launch_dma(const ConvArgs& a, hipStream_t st) {
 static int conv3x3_entry(const qv2x_conv_desc* d, const int8_t* in, const int8_t* w, const float* scale, const int32_t* corr, const int32_t* aw,
                          const float* bias, int res_mode, const void* res, int res_zx, float res_delta, int8_t* out, void* stream) {
     using namespace qv2x;
-    if (!d || !in || !w || !scale || !corr || !aw || !bias || !out) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8: null pointer");
+    if (any_null(d, in, w, scale, corr, aw, bias, out)) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8: null pointer");
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || (d->stride != 1 && d->stride != 2))
         return fail(QV2X_EINVAL, "qv2x_conv3x3_i8: bad shape n=%d h=%d w=%d stride=%d", d->n, d->h, d->w, d->stride);
     if (d->ngroups < 1 || d->ngroups > QV2X_MAX_GROUPS) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8: 1..%d input groups", QV2X_MAX_GROUPS);
     if (d->cout % 64 || d->cin_total % 16 || d->out_ctotal < d->out_c0 + d->cout)
         return fail(QV2X_EALIGN, "qv2x_conv3x3_i8: cout %% 64, cin_total %% 16, out channel window");
-    if (((uintptr_t)in & 15) || ((uintptr_t)w & 15) || ((uintptr_t)out & 15)) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8: in / w / out must be 16-byte aligned");
+    if (misaligned16(in, w, out)) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8: in / w / out must be 16-byte aligned");
     if (d->out_ctotal % 16 || d->out_c0 % 16) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8: out_ctotal and out_c0 must be multiples of 16");
     ConvArgs a;
     a.res = res; a.res_ax = 128 - res_zx; a.res_delta = res_delta;
     a.in = in; a.w = w; a.scale = scale; a.corr = corr; a.aw = aw; a.bias = bias; a.out = out;
     a.n = d->n; a.hp = d->h + 2; a.wp = d->w + 2; a.cin_total = d->cin_total; a.stride = d->stride; a.cout = d->cout;
     a.ngroups = d->ngroups;
-    a.ktot = 0;
+    const GroupWalk gw = walk_groups(d);
+    if (gw.bad >= 0) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8: " QV2X_GROUP_RULE, gw.bad, d->group_c0[gw.bad], d->group_c[gw.bad]);
+    a.ktot = 9 * 64 * gw.chunks;
     for (int g = 0; g < QV2X_MAX_GROUPS; ++g) {
         a.gc0[g] = g < d->ngroups ? d->group_c0[g] : 0;
         a.gc[g] = g < d->ngroups ? d->group_c[g] : 0;
-        if (g < d->ngroups) {
-            if (a.gc[g] <= 0 || a.gc[g] % 64 || a.gc0[g] % 16 || a.gc0[g] + a.gc[g] > d->cin_total)
-                return fail(QV2X_EALIGN, "qv2x_conv3x3_i8: group %d (c0=%d, c=%d): channels must come in multiples of 64", g, a.gc0[g], a.gc[g]);
-            a.ktot += 9 * a.gc[g];
-        }
     }
-    a.ho = (d->h + 2 - 3) / d->stride + 1;
-    a.wo = (d->w + 2 - 3) / d->stride + 1;
+    a.ho = conv_out(d->h, d->stride); a.wo = conv_out(d->w, d->stride);
     a.M = d->n * a.ho * a.wo;
     a.out_ctotal = d->out_ctotal; a.out_c0 = d->out_c0; a.relu = d->relu;
     a.out_delta = d->out_delta; a.out_zp = d->out_zp;
@@ -378,7 +375,7 @@ static int conv3x3_entry(const qv2x_conv_desc* d, const int8_t* in, const int8_t
     for (int g = 0; g < a.ngroups; ++g) k128 = k128 && (a.gc[g] % 128 == 0);
     const bool multi = a.ngroups > 1;
     if (res_mode) {
-        if (multi || a.cout != 64 || a.gc[0] != 64 || !res || ((uintptr_t)res & 15) || (res_mode != 2 && res_mode != 3))
+        if (multi || a.cout != 64 || a.gc[0] != 64 || !res || misaligned16(res) || (res_mode != 2 && res_mode != 3))
             return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_res: one input group of 64 channels, cout 64, res_mode 2 | 3, aligned shortcut");
         return res_mode == 2 ? launch_dma<64, 64, 2, 2, 64, false, 3, 4, 2>(a, st) : launch_dma<64, 64, 2, 2, 64, false, 3, 4, 3>(a, st);   // (four workgroups per CU: the shortcut epilogue spilled 104 bytes at six, 28 at five)
     }
@@ -396,7 +393,7 @@ static int conv3x3_entry(const qv2x_conv_desc* d, const int8_t* in, const int8_t
     // 256-byte K chunks (fewest barriers, 98 KB of LDS: one workgroup per CU) while the grid fits the chip in one round; beyond
     // that two resident workgroups per CU with 128-byte chunks win (25 x 88 x 256 layers: 10.0 vs 10.9 us for one frame, 27.0 vs
     // 21.1 us for a batch of four, profiles/r02_conv_dispatch_ablation.log)
-    const long long wgs64 = (long long)((a.M + 63) / 64) * (a.cout / 64);
+    const long long wgs64 = (long long)tiles(a.M, 64) * (a.cout / 64);
     if (a.gc[0] % 256 == 0 && (QV2X_CONV_FORCE ? QV2X_CONV_FORCE < 2 : wgs64 <= 256)) return launch_dma<64, 64, 2, 2, 256, false, 3, 1>(a, st);
     // three stages rather than four: the extra resident workgroup (3 or 6 per CU) hides more latency than the fourth stage did
     // (64->64 layer at batch 8: 38.7 -> 32.4 us; 25x88 128-channel layer at batch 4: 20.4 -> 15.7 us)

@@ -19,7 +19,8 @@
 //     input (2r + dy, 2c + dx) is again a pure shift inside plane (dy & 1, dx & 1).
 //   * arithmetic is the single-group case of conv_i8.hip (exact i32 sums, zero-point correction from v_dot4 window sums,
 //     y = bias + float(T) * scale, ReLU, q_pack4 = clamp(rint(fma(y, fl(1 / delta), zp)), 0, 255)): bit-identical to oracle/qv2x_oracle.c:orc_conv3x3 layer by layer.
-#include "common.h"
+#include "conv_host.h"
+#include "conv_i8_dev.h"
 
 #ifndef QV2X_CHAIN_DBG
 #define QV2X_CHAIN_DBG 0      // dev builds (tools/bench_chain_abl.py): 1 no epilogue math, 2 no K loop, 3 no input DMA, 4 weights loaded once
@@ -37,9 +38,6 @@ struct ChainArgs {
     float out_delta[MAXD], out_zp[MAXD];
 };
 
-template <int V> struct IC { static constexpr int value = V; };
-
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 // geometry of layer d of a D-layer chain over a TH x TW patch
@@ -49,12 +47,12 @@ struct Geo {
     static constexpr int cols(int d) { return TW + 2 * (D - 1 - d); }
     static constexpr int pitch(int d) { return (d == 0 && S0 == 2) ? cols(0) + 1 : cols(d) + 2; }     // input pitch of layer d
     static constexpr int M(int d) { return (rows(d) - 1) * pitch(d) + cols(d); }
-    static constexpr int MT(int d) { return cdiv(M(d), 32); }
+    static constexpr int MT(int d) { return tiles(M(d), 32); }
     // farthest input pixel a (possibly garbage) lane of layer d touches, relative to its plane / region base
     static constexpr int reach(int d) { return MT(d) * 32 + ((d == 0 && S0 == 2) ? pitch(0) + 1 : 2 * pitch(d) + 2); }
     // layer-0 input: stride 2 -> four parity planes, each padded to 16 pixels; stride 1 -> one plane
     static constexpr int plane_px(int p) {
-        return S0 == 2 ? cdiv((rows(0) + ((p >> 1) == 0 ? 1 : 0)) * pitch(0), 16) * 16 : cdiv((rows(0) + 2) * pitch(0), 16) * 16;
+        return S0 == 2 ? tiles((rows(0) + ((p >> 1) == 0 ? 1 : 0)) * pitch(0), 16) * 16 : tiles((rows(0) + 2) * pitch(0), 16) * 16;
     }
     static constexpr int plane_off(int p) { return p == 0 ? 0 : plane_off(p - 1) + plane_px(p - 1); }
     static constexpr int NPLANE = S0 == 2 ? 4 : 1;
@@ -66,7 +64,7 @@ struct Geo {
             if (((d & 1) ? 0 : 1) == a) v = cmax(v, rows(d) * cols(d));          // written by layer d
             if (d >= 1 && (((d - 1) & 1) ? 0 : 1) == a) v = cmax(v, reach(d));     // read by layer d
         }
-        return cdiv(v, 16) * 16;
+        return tiles(v, 16) * 16;
     }
 };
 
@@ -87,7 +85,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_i8_chain64_kernel(const ChainA
         const int Yo = y0 - (D - 1), Xo = x0 - (D - 1);                // image coordinates of output (0, 0) of layer 0's region
         constexpr int NBLK = G::in_px / 16;
 #pragma unroll
-        for (int j = 0; j < cdiv(NBLK, 8); ++j) {
+        for (int j = 0; j < tiles(NBLK, 8); ++j) {
             const int blk = wave + 8 * j;
             if (blk < NBLK && QV2X_CHAIN_DBG != 3) {
                 const int q = blk * 16 + (lane >> 2), slot = lane & 3;
@@ -167,10 +165,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_i8_chain64_kernel(const ChainA
                 if (QV2X_CHAIN_DBG == 6) { f0 = breg[(tap * 2 + 3) % 18]; f1 = breg[(tap * 2 + 5) % 18]; }      // no LDS reads
                 else { f0 = *(const v4i*)(st + off[tap]); f1 = *(const v4i*)(st + (off[tap] ^ 32)); }
                 if (QV2X_CHAIN_DBG != 5) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) xs = __builtin_amdgcn_sdot4(f0[q], 0x01010101, xs, false);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) xs = __builtin_amdgcn_sdot4(f1[q], 0x01010101, xs, false);
+                    xs = sum16(f1, sum16(f0, xs));
                 } else xs += f0[0] + f1[3];
                 if (QV2X_CHAIN_DBG != 7) {
                     acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(breg[tap * 2], f0, acc, 0, 0, 0);
@@ -212,14 +207,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_i8_chain64_kernel(const ChainA
         const int8_t* reg = lds + (((D - 1) & 1) ? 0 : A0);
         constexpr int UNITS = TH * TW * 4;
 #pragma unroll
-        for (int k = 0; k < cdiv(UNITS, 512); ++k) {
+        for (int k = 0; k < tiles(UNITS, 512); ++k) {
             const int u = tid + k * 512;
             if (u < UNITS) {
                 const int op = u >> 2, slot = u & 3, sub = slot ^ ((op >> 2) & 3);
                 const int ro = op / TW, cc = op - ro * TW;
                 const int Y = y0 + ro, X = x0 + cc;
                 if (Y < a.h && X < a.w_)
-                    *(v4i*)(a.out + ((size_t)(img * (a.h + 2) + Y + 1) * (a.w_ + 2) + X + 1) * CH + sub * 16) = *(const v4i*)(reg + op * CH + slot * 16);
+                    *(v4i*)(a.out + QV2X_BEV_PIXEL(size_t, img, Y, X, a.h, a.w_) * CH + sub * 16) = *(const v4i*)(reg + op * CH + slot * 16);
             }
         }
     }
@@ -231,16 +226,16 @@ __global__ __launch_bounds__(512, 1) void conv3x3_i8_chain64_kernel(const ChainA
 extern "C" int qv2x_conv3x3_i8_chain64(const qv2x_chain_desc* d, const int8_t* in, const int8_t* w_chain, const float* scale,
                                        const int32_t* corr, const int32_t* aw, const float* bias, int8_t* out, void* stream) {
     using namespace qv2x;
-    if (!d || !in || !w_chain || !scale || !corr || !aw || !bias || !out) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_chain64: null pointer");
+    if (any_null(d, in, w_chain, scale, corr, aw, bias, out)) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_chain64: null pointer");
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || (d->stride0 != 1 && d->stride0 != 2))
         return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_chain64: bad shape n=%d h=%d w=%d stride0=%d", d->n, d->h, d->w, d->stride0);
     if (d->depth < 1 || d->depth > MAXD) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_chain64: 1..%d layers", MAXD);
-    if (((uintptr_t)in & 15) || ((uintptr_t)w_chain & 15) || ((uintptr_t)out & 15)) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8_chain64: in / w / out must be 16-byte aligned");
+    if (misaligned16(in, w_chain, out)) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8_chain64: in / w / out must be 16-byte aligned");
     ChainArgs a;
     a.in = in; a.w = w_chain; a.scale = scale; a.corr = corr; a.aw = aw; a.bias = bias; a.out = out;
     a.n = d->n; a.h = d->h; a.w_ = d->w; a.relu = d->relu;
-    // layer 0 is a padding-1 convolution of the in_h x in_w map: (in + 2 - 3) / stride + 1 outputs per axis
-    if ((d->in_h + 2 - 3) / d->stride0 + 1 != d->h || (d->in_w + 2 - 3) / d->stride0 + 1 != d->w)
+    // layer 0 is a padding-1 convolution of the in_h x in_w map
+    if (conv_out(d->in_h, d->stride0) != d->h || conv_out(d->in_w, d->stride0) != d->w)
         return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_chain64: a %d x %d input does not give %d x %d at stride %d", d->in_h, d->in_w, d->h, d->w, d->stride0);
     a.hin_p = d->in_h + 2; a.win_p = d->in_w + 2;                     // padded size of the input tensor
     for (int l = 0; l < MAXD; ++l) {
@@ -249,7 +244,7 @@ extern "C" int qv2x_conv3x3_i8_chain64(const qv2x_chain_desc* d, const int8_t* i
         if (l < d->depth && !(d->out_delta[l] > 0.0f)) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_chain64: out_delta must be positive");
     }
     constexpr int TH = 5, TW = 32;
-    a.tiles_x = (a.w_ + TW - 1) / TW; a.tiles_y = (a.h + TH - 1) / TH;
+    a.tiles_x = tiles(a.w_, TW); a.tiles_y = tiles(a.h, TH);
     const dim3 grid(a.n * a.tiles_x * a.tiles_y);
     hipStream_t st = (hipStream_t)stream;
 #define QV2X_CHAIN(D, S) conv3x3_i8_chain64_kernel<TH, TW, D, S><<<grid, 512, 0, st>>>(a)

@@ -12,20 +12,12 @@
 //     straight from L2 to registers: a wave only ever reads ITS OWN 32 rows of a tile, so the LDS ring of round 1 (16 KB written
 //     and 16 KB read per step, a workgroup barrier per step) bought nothing but asynchrony.  Two 16-byte loads per lane per
 //     step, a ring of three steps; LDS holds the two halo tiles only and the waves meet once per 64-channel chunk (nine steps).
-#include "common.h"
+#include "conv_i8_wide.h"
+#include "conv_i8_dev.h"
 
 #include <cstdlib>
 
 namespace qv2x {
-
-// conv_i8_ws.hip: the weights-stationary form for layers with 64 input channels (same w_wide layout, same results)
-bool ws64_takes(const qv2x_conv_desc* d);
-// conv_i8_ws2.hip: the weights-stationary STRIDE-2 form for 64 input channels (cout 64 | 128)
-bool ws2_takes(const qv2x_conv_desc* d);
-int launch_ws2(const qv2x_conv_desc* d, const int8_t* in, const int8_t* w_wide, const float* scale, const int32_t* corr, const int32_t* aw,
-               const float* bias, int8_t* out, hipStream_t st);
-int launch_ws64(const qv2x_conv_desc* d, const int8_t* in, const int8_t* w_wide, const float* scale, const int32_t* corr, const int32_t* aw,
-                const float* bias, int8_t* out, hipStream_t st);
 
 namespace {
 
@@ -36,23 +28,7 @@ constexpr int HBLK = 4 * (HPAD / 64);                                  // 16 DMA
 constexpr int HBUF = 4 * PLANE;                                        // 16 KiB per halo tile
 constexpr int BM = TH * TW, WTILE = 256;                               // pixels per workgroup; rows of one pre-tiled weight tile
 constexpr int MT = 5;
-constexpr int MAX_CHUNKS = 24;
-
-struct WideArgs {
-    const int8_t* in; const int8_t* wt; const float* scale; const int* corr; const int* aw; const float* bias; int8_t* out;
-    int n, hp, wp, cin_total, cout, ho, wo, tiles_x, tiles_y;
-    int out_ctotal, out_c0, relu;
-    float out_delta, out_zp;
-    int nchunks, ngroups;
-    int wtile;                        // rows of one pre-tiled weight tile: min(cout, 256)
-    int cend[QV2X_MAX_GROUPS];        // first chunk index past group g
-    int coff[MAX_CHUNKS];             // channel byte offset of each 64-channel chunk inside a pixel
-    int items;                        // (patch, channel block) pairs, patches padded to a multiple of 8
-    int nsteps;                       // weight steps of an item's K loop: 9 per 64 input channels
-    int stride2;                      // 1: the stride-2 form (four parity-plane chunks per 64 input channels)
-};
-
-template <int V> struct IC { static constexpr int value = V; };
+struct WideArgs : WideFields {};      // (conv_i8_wide.h: the fields; the kernels' symbols carry this name)
 
 #if defined(QV2X_WABL) && QV2X_WABL == 1      // dev ablation: no MFMAs, the operands stay live
 __device__ __forceinline__ v16i wabl_nomfma(v4i a, v4i b, v16i c) { c[0] += a[0] + b[0]; c[1] += a[3] ^ b[3]; return c; }
@@ -203,9 +179,7 @@ __global__ __launch_bounds__(NW * 64, QV2X_WIDE_BOUNDS(MULTI, NW)) void conv3x3_
 #pragma unroll
         for (int j = 0; j < LH; ++j) {
             const int blk = wave + NW * j;
-            int s = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s = __builtin_amdgcn_sdot4(v[j][q], 0x01010101, s, false);
+            const int s = sum16(v[j]);
             __hip_atomic_fetch_add(psum + slot * HPAD + (blk & 3) * 64 + lane, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     };
@@ -469,17 +443,12 @@ __global__ __launch_bounds__(NW * 64, QV2X_WIDE_BOUNDS(MULTI, NW)) void conv3x3_
                 pk[i][g4] = q_pack4(y[0], y[1], y[2], y[3], a.out_delta, rd, a.out_zp, lowc);
                 // A tile leaves as soon as its last quad is packed.  (Five stores back to back behind the whole epilogue showed as 2.9k cycles
                 // of "store issue" per item in the phase stamps; spreading them over the last quad pass changes no layer's time -- the
-                // epilogue is bound by the SIMD's VALU issue, the stores only took the blame.)  No LDS staging: the half-wave exchange
-                // v_permlane32_swap turns the lane's four channel quads (0-3 | 8-11 | 16-19 | 24-27 in the lower half-wave, +4 in the upper)
-                // into 16 contiguous channels -- lower half 0-15, upper half 16-31 of the same pixel.
+                // epilogue is bound by the SIMD's VALU issue, the stores only took the blame.)  No LDS staging: gather16 (conv_i8_dev.h).
                 if (g4 == 3) {
-                    const auto s02 = __builtin_amdgcn_permlane32_swap(pk[i][0], pk[i][2], false, false);
-                    const auto s13 = __builtin_amdgcn_permlane32_swap(pk[i][1], pk[i][3], false, false);
-                    v4i ob;
-                    ob[0] = s02[0]; ob[1] = s02[1]; ob[2] = s13[0]; ob[3] = s13[1];
+                    const v4i ob = gather16(pk[i]);
                     const int yo = cur.y0 + i, xo = cur.x0 + (lane & 31);
                     if (yo < a.ho && xo < a.wo)
-                        *(v4i*)(a.out + ((size_t)(cur.img * (a.ho + 2) + yo + 1) * (a.wo + 2) + xo + 1) * a.out_ctotal + a.out_c0 + n0 + wave * 32 + half * 16) = ob;
+                        *(v4i*)(a.out + QV2X_BEV_PIXEL(size_t, cur.img, yo, xo, a.ho, a.wo) * a.out_ctotal + a.out_c0 + n0 + wave * 32 + half * 16) = ob;
                 }
             }
         }
@@ -537,42 +506,38 @@ __global__ void pack_wide_kernel(const int8_t* __restrict__ w, int8_t* __restric
     *(v4i*)(wt + u * 16) = *(const v4i*)(w + (size_t)(nb * a.wtile + row) * ktot + k);
 }
 
-int fill_args(const qv2x_conv_desc* d, WideArgs& a) {
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: bad shape n=%d h=%d w=%d", d->n, d->h, d->w);
+// `quiet`: the same rules without a message (qv2x_conv3x3_i8_wide_ok asks; qv2x_last_error() stays what it was)
+int fill_args(const qv2x_conv_desc* d, WideArgs& a, bool quiet = false) {
+    auto refuse = [quiet](int code, const char* fmt, auto... v) { return quiet ? code : fail(code, fmt, v...); };
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0) return refuse(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: bad shape n=%d h=%d w=%d", d->n, d->h, d->w);
     if ((d->stride != 1 && d->stride != 2) || (d->cout != 64 && d->cout != 128 && d->cout % 256))
-        return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: stride 1 | 2 and cout 64 | 128 | a multiple of 256");
-    if (d->stride == 2 && d->ngroups != 1) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: the stride-2 form takes one input group");
-    if (d->cout < 256 && d->ngroups != 1) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: the 64 / 128-channel form takes one input group");
+        return refuse(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: stride 1 | 2 and cout 64 | 128 | a multiple of 256");
+    if (d->stride == 2 && d->ngroups != 1) return refuse(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: the stride-2 form takes one input group");
+    if (d->cout < 256 && d->ngroups != 1) return refuse(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: the 64 / 128-channel form takes one input group");
     a.wtile = d->cout < 256 ? d->cout : 256;
-    if (d->ngroups < 1 || d->ngroups > QV2X_MAX_GROUPS) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: 1..%d input groups", QV2X_MAX_GROUPS);
+    if (d->ngroups < 1 || d->ngroups > QV2X_MAX_GROUPS) return refuse(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: 1..%d input groups", QV2X_MAX_GROUPS);
     if (d->cin_total % 16 || d->out_ctotal % 16 || d->out_c0 % 16 || d->out_ctotal < d->out_c0 + d->cout)
-        return fail(QV2X_EALIGN, "qv2x_conv3x3_i8_wide: cin_total, out_ctotal, out_c0 %% 16; out channel window");
-    if (!(d->out_delta > 0.0f)) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: out_delta must be positive");
+        return refuse(QV2X_EALIGN, "qv2x_conv3x3_i8_wide: cin_total, out_ctotal, out_c0 %% 16; out channel window");
+    if (!(d->out_delta > 0.0f)) return refuse(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: out_delta must be positive");
     a.n = d->n; a.hp = d->h + 2; a.wp = d->w + 2; a.cin_total = d->cin_total; a.cout = d->cout;
     a.stride2 = d->stride == 2;
-    a.ho = (d->h + 2 - 3) / d->stride + 1; a.wo = (d->w + 2 - 3) / d->stride + 1;     // (stride 1: h x w)
-    a.tiles_x = (a.wo + TW - 1) / TW; a.tiles_y = (a.ho + TH - 1) / TH;
+    a.ho = conv_out(d->h, d->stride); a.wo = conv_out(d->w, d->stride);               // (stride 1: h x w)
+    a.tiles_x = tiles(a.wo, TW); a.tiles_y = tiles(a.ho, TH);
     a.out_ctotal = d->out_ctotal; a.out_c0 = d->out_c0; a.relu = d->relu; a.out_delta = d->out_delta; a.out_zp = d->out_zp;
     a.ngroups = d->ngroups;
+    // (a chunk too many in front of a bad group is the fault reported: the groups are taken in order)
+    const GroupWalk gw = walk_groups(d);
+    if (gw.chunks > MAX_CHUNKS) return refuse(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: more than %d 64-channel chunks", MAX_CHUNKS);
+    if (gw.bad >= 0) return refuse(QV2X_EALIGN, "qv2x_conv3x3_i8_wide: " QV2X_GROUP_RULE, gw.bad, d->group_c0[gw.bad], d->group_c[gw.bad]);
     int n = 0;
     for (int g = 0; g < QV2X_MAX_GROUPS; ++g) {
-        if (g < d->ngroups) {
-            const int c0 = d->group_c0[g], c = d->group_c[g];
-            if (c <= 0 || c % 64 || c0 % 16 || c0 + c > d->cin_total)
-                return fail(QV2X_EALIGN, "qv2x_conv3x3_i8_wide: group %d (c0=%d, c=%d): channels must come in multiples of 64", g, c0, c);
-            for (int cc = 0; cc < c / 64; ++cc) {
-                if (n >= MAX_CHUNKS) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: more than %d 64-channel chunks", MAX_CHUNKS);
-                a.coff[n++] = c0 + cc * 64;
-            }
-            a.cend[g] = n;
-        } else {
-            a.cend[g] = 1 << 30;
-        }
+        for (int cc = 0; g < d->ngroups && cc < d->group_c[g] / 64; ++cc) a.coff[n++] = d->group_c0[g] + cc * 64;
+        a.cend[g] = g < d->ngroups ? n : 1 << 30;
     }
     a.nchunks = n;
     a.nsteps = 9 * n;
     if (a.stride2) {                                                   // chunk = (64 channels, parity plane): four per 64 channels
-        if (4 * n > MAX_CHUNKS) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: stride 2 takes at most %d input channels", MAX_CHUNKS / 4 * 64);
+        if (4 * n > MAX_CHUNKS) return refuse(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: stride 2 takes at most %d input channels", MAX_CHUNKS / 4 * 64);
         for (int c = 4 * n - 1; c >= 0; --c) a.coff[c] = a.coff[c / 4];
         a.nchunks = 4 * n;
         a.cend[0] = 4 * n;
@@ -585,15 +550,11 @@ int fill_args(const qv2x_conv_desc* d, WideArgs& a) {
 }  // namespace qv2x
 
 // output channels per workgroup: 256 (8 waves) while that fills the chip, else 128 (4 waves), 64 for the 64-channel layers
-static long long wide_patches(const qv2x_conv_desc* d) {
-    const int ho = (d->h + 2 - 3) / d->stride + 1, wo = (d->w + 2 - 3) / d->stride + 1;      // output map (stride 1: h x w)
-    return (long long)d->n * ((ho + qv2x::TH - 1) / qv2x::TH) * ((wo + qv2x::TW - 1) / qv2x::TW);
-}
+static long long wide_patches(const qv2x::WideArgs& a) { return (long long)a.n * a.tiles_x * a.tiles_y; }
 
-static int wide_bn(const qv2x_conv_desc* d) {
-    const long long patches = wide_patches(d);
-    if (d->cout % 256 == 0) return patches * (d->cout / 256) >= 192 ? 256 : 128;
-    return d->cout;
+static int wide_bn(const qv2x::WideArgs& a) {
+    if (a.cout % 256 == 0) return wide_patches(a) * (a.cout / 256) >= 192 ? 256 : 128;
+    return a.cout;
 }
 
 #ifdef QV2X_WIDE_FINE
@@ -623,28 +584,23 @@ extern "C" __attribute__((visibility("default"))) int qv2x_debug_wide_trace_clea
 #endif
 
 extern "C" int qv2x_conv3x3_i8_wide_ok(const qv2x_conv_desc* d) {
-    if (!d || (d->stride != 1 && d->stride != 2) || (d->cout != 64 && d->cout != 128 && d->cout % 256) || d->ngroups < 1 || d->ngroups > QV2X_MAX_GROUPS) return 0;
-    if ((d->cout < 256 || d->stride == 2) && d->ngroups != 1) return 0;
-    int chunks = 0;
-    for (int g = 0; g < d->ngroups; ++g) {
-        if (d->group_c[g] <= 0 || d->group_c[g] % 64 || d->group_c0[g] % 16) return 0;
-        chunks += d->group_c[g] / 64;
-    }
+    qv2x::WideArgs a{};
+    if (!d || qv2x::fill_args(d, a, true)) return 0;                   // what qv2x_conv3x3_i8_wide refuses
     // enough workgroups (a 5 x 32 patch x 64 / 128 / 256 output channels each) to fill the chip: below that the 64 x 64-tile kernel
     // of qv2x_conv3x3_i8 spreads the layer over more CUs
-    const long long patches = wide_patches(d);
-    const long long wgs = patches * (d->cout / wide_bn(d));
+    const long long patches = wide_patches(a);
+    const long long wgs = patches * (d->cout / wide_bn(a));
     // Stride 2 (measured, batch of 32 / 8): four tiles, barriers and window-sum passes per nine K steps instead of one -- 256 output
     // channels amortise them (34 vs 39 us, 13.8 vs 17.6 us), 128 do not (46 vs 44 us) and 64 lose (149 vs 129 us on the 192-pixel im2col tiles)
     if (qv2x::ws2_takes(d)) return 1;                                  // stride 2, 64 input channels: the weights-stationary form (conv_i8_ws2.hip)
     if (d->stride == 2 && d->cout % 256) return 0;
-    return chunks * (d->stride == 2 ? 4 : 1) <= qv2x::MAX_CHUNKS && patches * qv2x::TH * qv2x::TW >= 16384 && wgs >= (d->cout == 64 ? 1024 : 192);
+    return patches * qv2x::TH * qv2x::TW >= 16384 && wgs >= (d->cout == 64 ? 1024 : 192);
 }
 
 extern "C" int qv2x_conv3x3_i8_pack_wide(const qv2x_conv_desc* d, const int8_t* w, int8_t* w_wide, void* stream) {
     using namespace qv2x;
-    if (!d || !w || !w_wide) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_pack_wide: null pointer");
-    if (((uintptr_t)w & 15) || ((uintptr_t)w_wide & 15)) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8_pack_wide: 16-byte alignment");
+    if (any_null(d, w, w_wide)) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_pack_wide: null pointer");
+    if (misaligned16(w, w_wide)) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8_pack_wide: 16-byte alignment");
     WideArgs a{};
     if (int rc = fill_args(d, a)) return rc;
     const int ktot = a.nsteps * 64;                                    // bytes of one output channel's weights
@@ -656,18 +612,18 @@ extern "C" int qv2x_conv3x3_i8_pack_wide(const qv2x_conv_desc* d, const int8_t* 
 extern "C" int qv2x_conv3x3_i8_wide(const qv2x_conv_desc* d, const int8_t* in, const int8_t* w_wide, const float* scale,
                                     const int32_t* corr, const int32_t* aw, const float* bias, int8_t* out, void* stream) {
     using namespace qv2x;
-    if (!d || !in || !w_wide || !scale || !corr || !aw || !bias || !out) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: null pointer");
-    if (((uintptr_t)in & 15) || ((uintptr_t)w_wide & 15) || ((uintptr_t)out & 15)) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8_wide: in / w / out must be 16-byte aligned");
+    if (any_null(d, in, w_wide, scale, corr, aw, bias, out)) return fail(QV2X_EINVAL, "qv2x_conv3x3_i8_wide: null pointer");
+    if (misaligned16(in, w_wide, out)) return fail(QV2X_EALIGN, "qv2x_conv3x3_i8_wide: in / w / out must be 16-byte aligned");
     WideArgs a{};
     if (int rc = fill_args(d, a)) return rc;
     a.in = in; a.wt = w_wide; a.scale = scale; a.corr = corr; a.aw = aw; a.bias = bias; a.out = out;
     hipStream_t st = (hipStream_t)stream;
 #ifndef QV2X_NO_WS64
-    if (ws64_takes(d)) return launch_ws64(d, in, w_wide, scale, corr, aw, bias, out, st);
-    if (ws2_takes(d)) return launch_ws2(d, in, w_wide, scale, corr, aw, bias, out, st);
+    if (ws64_takes(d)) return launch_ws64(a, st);
+    if (ws2_takes(d)) return launch_ws2(a, st);
 #endif
-    const int patches8 = (a.n * a.tiles_x * a.tiles_y + 7) / 8 * 8;   // block ids come in groups of 8 (one per XCD)
-    const int bn = wide_bn(d);
+    const int patches8 = tiles(a.n * a.tiles_x * a.tiles_y, 8) * 8;   // block ids come in groups of 8 (one per XCD)
+    const int bn = wide_bn(a);
     a.items = patches8 * (a.cout / bn);
     // persistent workgroups: one round of what a CU holds (two waves per SIMD: 174-256 VGPRs; LDS 36-60 KB per workgroup), a multiple
     // of 8 * (cout / bn)

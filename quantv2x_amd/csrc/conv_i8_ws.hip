@@ -16,7 +16,8 @@
 //   * with the accumulators independent of the patch height, a workgroup takes 10 x 32 patches (4 waves = 2 channel blocks x 2 row
 //     groups of 5 rows): 12 x 34 / (10 x 32) = 1.28 halo bytes per pixel instead of 1.49.
 // The halo tile, its planar LDS layout, the LDS-DMA and the per-pixel channel sums are those of conv_i8_wide.hip.
-#include "common.h"
+#include "conv_i8_wide.h"
+#include "conv_i8_dev.h"
 
 namespace qv2x {
 
@@ -31,8 +32,6 @@ struct WsArgs {
     float out_delta, out_zp;
     int items;
 };
-
-template <int V> struct IC { static constexpr int value = V; };
 
 #ifdef QV2X_WS_FINE         // dev build only (tools/ws_fine.py): s_memtime stamps of wave 0 during the workgroup's THIRD item
 __device__ long long g_ws_fine[4096 * 16];
@@ -49,8 +48,8 @@ template <int NCB, int RG, int ROWS>
 __global__ __launch_bounds__(NCB * RG * 64, NCB * RG == 4 ? 2 : 1) void conv3x3_i8_ws64_kernel(const WsArgs a) {
     constexpr int NW = NCB * RG;
     static_assert(NW == 4 || NW == 8, "four or eight waves");
-    constexpr int TH = RG * ROWS, HPIX = (TH + 2) * HWD, HPAD = (HPIX + 63) / 64 * 64, PLANE = HPAD * 16, HBUF = 4 * PLANE;
-    constexpr int HBLK = 4 * (HPAD / 64), LH = (HBLK + NW - 1) / NW;   // 1 KiB DMA pieces per halo tile; per wave
+    constexpr int TH = RG * ROWS, HPIX = (TH + 2) * HWD, HPAD = tiles(HPIX, 64) * 64, PLANE = HPAD * 16, HBUF = 4 * PLANE;
+    constexpr int HBLK = 4 * (HPAD / 64), LH = tiles(HBLK, NW);   // 1 KiB DMA pieces per halo tile; per wave
     static_assert(2 * PLANE + (2 * HWD + 2) * 16 + (ROWS - 1) * HWD * 16 < 65536, "fragment reads: base register + 16-bit immediate");
     __shared__ __attribute__((aligned(16))) int8_t lds[2 * HBUF + 2 * HPAD * 4];
     int8_t* hbuf = lds;
@@ -104,9 +103,7 @@ __global__ __launch_bounds__(NCB * RG * 64, NCB * RG == 4 ? 2 : 1) void conv3x3_
         for (int j = 0; j < LH; ++j) {
             const int blk = wave_u + NW * j;
             if (HBLK % NW != 0 && blk >= HBLK) break;
-            int s = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s = __builtin_amdgcn_sdot4(v[j][q], 0x01010101, s, false);
+            const int s = sum16(v[j]);
             __hip_atomic_fetch_add(psum + set * HPAD + (blk % (HPAD / 64)) * 64 + lane, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     };
@@ -150,23 +147,15 @@ __global__ __launch_bounds__(NCB * RG * 64, NCB * RG == 4 ? 2 : 1) void conv3x3_
     // behind every fourth MFMA left 14 gaps empty and made 4 too long (SQ counters: 28 % MFMA-busy, 42 % VALU-busy, 30 % issue stalls).
     const float qlow = lowc - 8388608.0f;
     unsigned qa = 0;
-    float yq[4];
     auto epi_one = [&](auto p_c, auto r_c) __attribute__((always_inline)) {
-        constexpr int P = decltype(p_c)::value, R = decltype(r_c)::value, G = R >> 2, E = R & 3;
+        constexpr int P = decltype(p_c)::value, R = decltype(r_c)::value;
 #if defined(QV2X_WS_ABL) && QV2X_WS_ABL == 1     // dev ablation (timing only): no epilogue at all, the sums stay live
         if (R == 0) asm volatile("" :: "v"(acc[P]));
         return;
 #endif
-        const int T = __mul24(awr[R], p_tot) + acc[P][R];              // (the channel's correction term went in as the first MFMA's C operand)
-        yq[E] = bs[R] + (float)T * sc[R];
-        if (E == 0) qa = 0;
-        q_add(yq[E], E, rd, a.out_zp, qlow, qa);                          // (common.h: fma + v_cvt_pk_u8_f32, two instructions per output)
-        if (E == 3) pk[G] = (int)(qa ^ 0x80808080u);
+        ws_requant<R>(acc[P][R], awr[R], p_tot, bs[R], sc[R], rd, a.out_zp, qlow, qa, pk);
         if (R == 15) {                                                 // half-wave exchange -> 16 contiguous channels per lane, one 16-byte store
-            const auto s02 = __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
-            const auto s13 = __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
-            v4i ob;
-            ob[0] = s02[0]; ob[1] = s02[1]; ob[2] = s13[0]; ob[3] = s13[1];
+            const v4i ob = gather16(pk);
 #if defined(QV2X_WS_ABL) && QV2X_WS_ABL == 5     // dev ablation: no stores
             asm volatile("" :: "v"(ob));
             if (false)
@@ -251,7 +240,7 @@ __global__ __launch_bounds__(NCB * RG * 64, NCB * RG == 4 ? 2 : 1) void conv3x3_
         p_tot = rs0 + rs1 + rs2; rs0 = rs1; rs1 = rs2;
         {
             const int row = cur.y0 + rg * ROWS + j, xo = cur.x0 + lane_x;
-            const long long off = ((long long)(cur.img * (a.ho + 2) + row + 1) * (a.wo + 2) + xo + 1) * a.out_ctotal + ch_off;
+            const long long off = QV2X_BEV_PIXEL(long long, cur.img, row, xo, a.ho, a.wo) * a.out_ctotal + ch_off;
             p_off = (row < a.ho && xo < a.wo) ? off : -1;
         }
         if (++j == ROWS) {
@@ -295,16 +284,9 @@ extern "C" __attribute__((visibility("default"))) int qv2x_debug_ws_fine_clear()
 #endif
 
 // called by qv2x_conv3x3_i8_wide (conv_i8_wide.hip) for the layers this form takes; the arguments are already validated there
-int launch_ws64(const qv2x_conv_desc* d, const int8_t* in, const int8_t* w_wide, const float* scale, const int32_t* corr, const int32_t* aw,
-                const float* bias, int8_t* out, hipStream_t st) {
+int launch_ws64(const WideFields& w, hipStream_t st) {
     WsArgs a{};
-    a.in = in; a.wt = w_wide; a.scale = scale; a.corr = corr; a.aw = aw; a.bias = bias; a.out = out;
-    a.n = d->n; a.hp = d->h + 2; a.wp = d->w + 2; a.cin_total = d->cin_total; a.cin_off = d->group_c0[0]; a.cout = d->cout;
-    a.ho = d->h; a.wo = d->w;
-    constexpr int TH = 10;
-    a.tiles_x = (a.wo + TW - 1) / TW; a.tiles_y = (a.ho + TH - 1) / TH;
-    a.out_ctotal = d->out_ctotal; a.out_c0 = d->out_c0; a.relu = d->relu; a.out_delta = d->out_delta; a.out_zp = d->out_zp;
-    a.items = a.n * a.tiles_x * a.tiles_y;
+    ws_args(a, w, 10);                                                 // <2, 2, 5>: patches of 10 x 32
     const int slots = 2 * 256;                                         // two four-wave workgroups per CU
     const dim3 grid(a.items < slots ? a.items : slots);
     conv3x3_i8_ws64_kernel<2, 2, 5><<<grid, 256, 0, st>>>(a);
@@ -313,8 +295,7 @@ int launch_ws64(const qv2x_conv_desc* d, const int8_t* in, const int8_t* w_wide,
 
 bool ws64_takes(const qv2x_conv_desc* d) {
     if (d->stride != 1 || d->ngroups != 1 || d->group_c[0] != 64 || d->cout != 64) return false;
-    const long long patches = (long long)d->n * ((d->h + 9) / 10) * ((d->w + TW - 1) / TW);
-    return patches >= 1024;                                            // two items per workgroup at least: the pipeline's fill is one row of 5
+    return (long long)d->n * tiles(d->h, 10) * tiles(d->w, TW) >= 1024;   // two items per workgroup at least: the pipeline's fill is one row of 5
 }
 
 }  // namespace qv2x

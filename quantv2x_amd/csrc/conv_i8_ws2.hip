@@ -21,7 +21,8 @@
 //     and TWO workgroups per CU: no barrier joins two waves of one SIMD (conv_i8_ws.hip), an item's fixed costs are paid per four or
 //     eight rows of a wave, and one workgroup's tile fetch hides behind the other's rows;
 //   * the per-pixel channel sums (for the weight zero-point term) are written, not accumulated: a quad of lanes holds one pixel.
-#include "common.h"
+#include "conv_i8_wide.h"
+#include "conv_i8_dev.h"
 
 namespace qv2x {
 
@@ -41,8 +42,6 @@ struct Ws2Args {
     int items;
     int tapstep[9];                    // weight step of tap t inside w_wide (qv2x_conv3x3_i8_pack_wide stores a stride-2 layer's taps plane by plane)
 };
-
-template <int V> struct IC { static constexpr int value = V; };
 
 // NCB 32-channel blocks x RG row groups = 4 waves; ROWS output rows per wave and item (RG * ROWS = TH)
 template <int NCB, int RG, int ROWS>
@@ -105,15 +104,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_i8_ws2_kernel(const Ws2Args a)
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int k = 16 * e + (lane >> 2);
-                if (k < IR) {
-                    v4i v; v[0] = xtra[e][0]; v[1] = xtra[e][1]; v[2] = xtra[e][2]; v[3] = xtra[e][3];
-                    *(v4i*)(lds + k * ROWB + 4096 + (lane & 3) * 16) = v;
-                }
-                int s = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) s = __builtin_amdgcn_sdot4(xtra[e][q], 0x01010101, s, false);
-                s += __builtin_amdgcn_mov_dpp(s, 0xB1, 0xf, 0xf, false);       // quad_perm [1,0,3,2]
-                s += __builtin_amdgcn_mov_dpp(s, 0x4E, 0xf, 0xf, false);       // quad_perm [2,3,0,1]
+                v4i v; v[0] = xtra[e][0]; v[1] = xtra[e][1]; v[2] = xtra[e][2]; v[3] = xtra[e][3];
+                if (k < IR) *(v4i*)(lds + k * ROWB + 4096 + (lane & 3) * 16) = v;
+                const int s = quad_sum64(v);
                 if (k < IR && (lane & 3) == 0) psum[k * PSW + 64] = s;
             }
         }
@@ -127,11 +120,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_i8_ws2_kernel(const Ws2Args a)
             for (int j = 0; j < N; ++j) v[j] = *(const v4i*)(lds + (J0 + j) * ROWB + wave_u * 1024 + lane * 16);
 #pragma unroll
             for (int j = 0; j < N; ++j) {
-                int s = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) s = __builtin_amdgcn_sdot4(v[j][q], 0x01010101, s, false);
-                s += __builtin_amdgcn_mov_dpp(s, 0xB1, 0xf, 0xf, false);
-                s += __builtin_amdgcn_mov_dpp(s, 0x4E, 0xf, 0xf, false);
+                const int s = quad_sum64(v[j]);
                 if ((lane & 3) == 0) psum[(J0 + j) * PSW + wave_u * 16 + (lane >> 2)] = s;
             }
         };
@@ -179,20 +168,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_i8_ws2_kernel(const Ws2Args a)
     const int ch_off = a.out_c0 + cb * 32 + half * 16;
     const float qlow = lowc - 8388608.0f;
     unsigned qa = 0;
-    float yq[4];
     // ONE output of the pending tile per call (conv_i8_ws.hip:epi_one): register R of its accumulator
     auto epi_one = [&](auto p_c, auto r_c) __attribute__((always_inline)) {
-        constexpr int P = decltype(p_c)::value, R = decltype(r_c)::value, G = R >> 2, E = R & 3;
-        const int T = __mul24(awr[R], p_tot) + acc[P][R];              // (the channel's correction term went in as the first MFMA's C operand)
-        yq[E] = bs[R] + (float)T * sc[R];
-        if (E == 0) qa = 0;
-        q_add(yq[E], E, rd, a.out_zp, qlow, qa);                          // (common.h: fma + v_cvt_pk_u8_f32, two instructions per output)
-        if (E == 3) pk[G] = (int)(qa ^ 0x80808080u);
+        constexpr int P = decltype(p_c)::value, R = decltype(r_c)::value;
+        ws_requant<R>(acc[P][R], awr[R], p_tot, bs[R], sc[R], rd, a.out_zp, qlow, qa, pk);
         if (R == 15) {                                                 // half-wave exchange -> 16 contiguous channels per lane, one 16-byte store
-            const auto s02 = __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
-            const auto s13 = __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
-            v4i ob;
-            ob[0] = s02[0]; ob[1] = s02[1]; ob[2] = s13[0]; ob[3] = s13[1];
+            const v4i ob = gather16(pk);
             if (p_off >= 0) *(v4i*)(a.out + p_off) = ob;
         }
     };
@@ -251,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_i8_ws2_kernel(const Ws2Args a)
         p_tot = rs0 + mid + rs2; rs0 = rs2;
         {
             const int row = cur.y0 + rg * ROWS + j, xo = cur.x0 + x;
-            const long long off = ((long long)(cur.img * (a.ho + 2) + row + 1) * (a.wo + 2) + xo + 1) * a.out_ctotal + ch_off;
+            const long long off = QV2X_BEV_PIXEL(long long, cur.img, row, xo, a.ho, a.wo) * a.out_ctotal + ch_off;
             p_off = (row < a.ho && xo < a.wo) ? off : -1;
         }
         if (++j == ROWS) {
@@ -292,29 +273,22 @@ __global__ __launch_bounds__(256, 2) void conv3x3_i8_ws2_kernel(const Ws2Args a)
 }  // namespace
 
 // called by qv2x_conv3x3_i8_wide (conv_i8_wide.hip) for the layers this form takes; the arguments are already validated there
-int launch_ws2(const qv2x_conv_desc* d, const int8_t* in, const int8_t* w_wide, const float* scale, const int32_t* corr, const int32_t* aw,
-               const float* bias, int8_t* out, hipStream_t st) {
+int launch_ws2(const WideFields& w, hipStream_t st) {
     Ws2Args a{};
-    a.in = in; a.wt = w_wide; a.scale = scale; a.corr = corr; a.aw = aw; a.bias = bias; a.out = out;
-    a.n = d->n; a.hp = d->h + 2; a.wp = d->w + 2; a.cin_total = d->cin_total; a.cin_off = d->group_c0[0]; a.cout = d->cout;
-    a.ho = (d->h + 2 - 3) / 2 + 1; a.wo = (d->w + 2 - 3) / 2 + 1;
-    a.tiles_x = (a.wo + TW - 1) / TW; a.tiles_y = (a.ho + TH - 1) / TH;
-    a.out_ctotal = d->out_ctotal; a.out_c0 = d->out_c0; a.relu = d->relu; a.out_delta = d->out_delta; a.out_zp = d->out_zp;
-    a.items = a.n * a.tiles_x * a.tiles_y;
+    ws_args(a, w, TH);
     // pack_wide stores a stride-2 layer's nine weight steps plane by plane -- taps 0 2 6 8 | 1 7 | 3 5 | 4 (conv_i8_wide.hip)
     const int s2step[9] = {0, 4, 1, 6, 8, 7, 2, 5, 3};
     for (int t = 0; t < 9; ++t) a.tapstep[t] = s2step[t];
     const int slots = 2 * 256;                                         // two four-wave workgroups per CU
     const dim3 grid(a.items < slots ? a.items : slots);
-    if (d->cout == 64) conv3x3_i8_ws2_kernel<2, 2, 4><<<grid, 256, 0, st>>>(a);
+    if (a.cout == 64) conv3x3_i8_ws2_kernel<2, 2, 4><<<grid, 256, 0, st>>>(a);
     else conv3x3_i8_ws2_kernel<4, 1, 8><<<grid, 256, 0, st>>>(a);
     return hip_check(hipGetLastError(), "qv2x_conv3x3_i8_wide (weights-stationary stride-2 form) launch");
 }
 
 bool ws2_takes(const qv2x_conv_desc* d) {
     if (d->stride != 2 || d->ngroups != 1 || d->group_c[0] != 64 || (d->cout != 64 && d->cout != 128)) return false;
-    const int ho = (d->h - 1) / 2 + 1, wo = (d->w - 1) / 2 + 1;
-    return (long long)d->n * ((ho + TH - 1) / TH) * ((wo + TW - 1) / TW) >= 1024;   // two items per workgroup at least
+    return (long long)d->n * tiles(conv_out(d->h, 2), TH) * tiles(conv_out(d->w, 2), TW) >= 1024;   // two items per workgroup at least
 }
 
 }  // namespace qv2x

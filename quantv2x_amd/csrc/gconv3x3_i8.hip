@@ -14,7 +14,8 @@
 // otherwise, and with one slab per workgroup every 128-byte line came up from L2 for 32 useful bytes (54 us for a 36 MB map) -- a wave
 // walks the patch's rows as 32-pixel MFMA tiles with its slab's weights (9 taps as A fragments, 36 VGPRs) in registers.  The WEIGHTS
 // are the A operand: a lane then owns one pixel and 16 channels in four runs of four (q_pack4).
-#include "common.h"
+#include "conv_host.h"
+#include "conv_i8_dev.h"
 
 namespace qv2x {
 namespace {
@@ -35,13 +36,13 @@ __global__ __launch_bounds__(256) void gconv3x3_i8_kernel(const GArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
     const int cbase = blockIdx.y * 128, nslab = min(4, (a.c - cbase) / 32);
     const int slab = blockIdx.y * 4 + wave, c0 = slab * 32;
-    const int tiles_x = (a.wo + TW - 1) / TW, tiles_y = (a.ho + TH - 1) / TH;
+    const int tiles_x = tiles(a.wo, TW), tiles_y = tiles(a.ho, TH);
     const int img = blockIdx.x / (tiles_x * tiles_y), trem = blockIdx.x - img * (tiles_x * tiles_y);
     const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
     {   // input patch: padded rows y0 S .. + PH, columns x0 S .. + PW (clamped into the padded map at the ragged edges: unused there)
         const int8_t* ibase = a.in + (size_t)img * (a.h + 2) * (a.wd + 2) * a.c + cbase;
         const int pieces = nslab * 2;                                // 16-byte pieces per pixel
-        constexpr int ITER = (PH * PW * 8 + 255) / 256;
+        constexpr int ITER = tiles(PH * PW * 8, 256);
         v4i tmp[ITER];                                               // every request in flight before the first LDS write
 #pragma unroll
         for (int it = 0; it < ITER; ++it) {
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256) void gconv3x3_i8_kernel(const GArgs a) {
         // the row's 32 pixels x 32 bytes leave as 16-byte stores: pixel lane >> 1, piece lane & 1
         const int yo = y0 + ty, xo = x0 + (lane >> 1);
         if (yo < a.ho && xo < a.wo)
-            *(v4i*)(a.out + ((size_t)(img * (a.ho + 2) + yo + 1) * (a.wo + 2) + xo + 1) * a.c + c0 + (lane & 1) * 16) =
+            *(v4i*)(a.out + QV2X_BEV_PIXEL(size_t, img, yo, xo, a.ho, a.wo) * a.c + c0 + (lane & 1) * 16) =
                 *(const v4i*)(stage + (lane >> 1) * SP + (lane & 1) * 16);
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
@@ -126,19 +127,18 @@ __global__ __launch_bounds__(256) void gconv3x3_i8_kernel(const GArgs a) {
 extern "C" int qv2x_gconv3x3_i8(const qv2x_gconv_desc* d, const int8_t* in, const int8_t* w_frag, const float* scale, const int32_t* corr,
                                 const int32_t* aw, const float* bias, int8_t* out, void* stream) {
     using namespace qv2x;
-    if (!d || !in || !w_frag || !scale || !corr || !aw || !bias || !out) return fail(QV2X_EINVAL, "qv2x_gconv3x3_i8: null pointer");
+    if (any_null(d, in, w_frag, scale, corr, aw, bias, out)) return fail(QV2X_EINVAL, "qv2x_gconv3x3_i8: null pointer");
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || (d->stride != 1 && d->stride != 2)) return fail(QV2X_EINVAL, "qv2x_gconv3x3_i8: bad shape / stride");
     if (d->c % 32 || (d->cg != 4 && d->cg != 8 && d->cg != 16)) return fail(QV2X_EALIGN, "qv2x_gconv3x3_i8: channels %% 32, 4 | 8 | 16 channels per group");
-    if (((uintptr_t)in & 15) || ((uintptr_t)w_frag & 15) || ((uintptr_t)out & 15) || ((uintptr_t)scale & 15) || ((uintptr_t)corr & 15) ||
-        ((uintptr_t)aw & 15) || ((uintptr_t)bias & 15)) return fail(QV2X_EALIGN, "qv2x_gconv3x3_i8: 16-byte aligned pointers");
+    if (misaligned16(in, w_frag, out, scale, corr, aw, bias)) return fail(QV2X_EALIGN, "qv2x_gconv3x3_i8: 16-byte aligned pointers");
     if (!(d->out_delta > 0.0f)) return fail(QV2X_EINVAL, "qv2x_gconv3x3_i8: out_delta must be positive");
     GArgs a;
     a.in = in; a.w = w_frag; a.scale = scale; a.corr = corr; a.aw = aw; a.bias = bias; a.out = out;
     a.n = d->n; a.h = d->h; a.wd = d->w; a.c = d->c; a.cg = d->cg; a.stride = d->stride;
-    a.ho = (d->h - 1) / d->stride + 1; a.wo = (d->w - 1) / d->stride + 1; a.M = d->n * a.ho * a.wo;
+    a.ho = conv_out(d->h, d->stride); a.wo = conv_out(d->w, d->stride); a.M = d->n * a.ho * a.wo;
     a.relu = d->relu; a.out_delta = d->out_delta; a.out_zp = d->out_zp;
     const int th = 4;
-    dim3 grid(a.n * ((a.ho + th - 1) / th) * ((a.wo + 31) / 32), (a.c + 127) / 128);
+    dim3 grid(a.n * tiles(a.ho, th) * tiles(a.wo, 32), tiles(a.c, 128));
     hipStream_t st = (hipStream_t)stream;
     if (a.stride == 1) gconv3x3_i8_kernel<1><<<grid, 256, 0, st>>>(a);
     else gconv3x3_i8_kernel<2><<<grid, 256, 0, st>>>(a);

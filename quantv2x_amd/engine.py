@@ -188,6 +188,36 @@ class _ConvLayer:
         assert np.abs(np.stack(corr)).max() < 2 ** 31
 
 
+def launch_conv3x3(lib, layer: _ConvLayer, x, n, h, w, out, out_q=None, res_mode=0, res=None, res_q=(0.0, 128), out_ctotal=None, out_c0=0,
+                   wide=True):
+    """One 3x3 QuantModule convolution on codes: ``qv2x_conv3x3_i8``, its wide form where ``wide`` and the shape allow it, or ``_res`` with a
+    fused residual end.  ``out_q``: the output quantizer (the layer's own by default); ``out_ctotal`` / ``out_c0``: the channel window of
+    ``out`` the layer writes (all of it by default).  Shared by every engine."""
+    out_q = layer.out_q if out_q is None else out_q
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.cin_total, d.stride, d.cout = n, h, w, x.shape[-1], layer.stride, layer.cout
+    d.ngroups = len(layer.groups)
+    for i, (c0, c, zx) in enumerate(layer.groups):
+        d.group_c0[i], d.group_c[i], d.group_zx[i] = c0, c, zx
+    d.out_ctotal = out.shape[-1] if out_ctotal is None else out_ctotal
+    d.out_c0, d.relu = out_c0, 1
+    d.out_delta, d.out_zp = out_q[0], float(out_q[1])
+    st = L.current_stream()
+    if res_mode:
+        L.check(lib.qv2x_conv3x3_i8_res(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
+                                        L.ptr(layer.bias), res_mode, L.ptr(res), int(res_q[1]), float(res_q[0]), L.ptr(out), st), layer.name)
+        return
+    if wide and lib.qv2x_conv3x3_i8_wide_ok(C.byref(d)):
+        if layer.w_wide is None:                                        # one-off re-tiling of the weights (not capturable)
+            layer.w_wide = torch.empty_like(layer.w)
+            L.check(lib.qv2x_conv3x3_i8_pack_wide(C.byref(d), L.ptr(layer.w), L.ptr(layer.w_wide), st), layer.name)
+        L.check(lib.qv2x_conv3x3_i8_wide(C.byref(d), L.ptr(x), L.ptr(layer.w_wide), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
+                                         L.ptr(layer.bias), L.ptr(out), st), layer.name)
+        return
+    L.check(lib.qv2x_conv3x3_i8(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
+                                L.ptr(layer.bias), L.ptr(out), st), layer.name)
+
+
 class _ChainLayers:
     """Consecutive 64 -> 64 channel conv layers of one backbone level as ONE launch (qv2x_conv3x3_i8_chain64): the B
     fragments of v_mfma_i32_32x32x32_i8 in load order ``[layer][cout/32][tap][cin/32][lane][16]`` and the per-layer
@@ -1030,23 +1060,7 @@ class DeployedModel(DeployedPostStage):
 
     # ---- kernel launch helpers -----------------------------------------------------------------------------
     def _conv(self, layer: _ConvLayer, x, n, h, w, out, out_ctotal=None, out_c0=0):
-        d = L.ConvDesc()
-        d.n, d.h, d.w, d.cin_total, d.stride, d.cout = n, h, w, x.shape[-1], layer.stride, layer.cout
-        d.ngroups = len(layer.groups)
-        for i, (c0, c, zx) in enumerate(layer.groups):
-            d.group_c0[i], d.group_c[i], d.group_zx[i] = c0, c, zx
-        d.out_ctotal = out.shape[-1] if out_ctotal is None else out_ctotal
-        d.out_c0, d.relu = out_c0, 1
-        d.out_delta, d.out_zp = layer.out_q[0], float(layer.out_q[1])
-        if self.use_wide_conv and self.lib.qv2x_conv3x3_i8_wide_ok(C.byref(d)):
-            if layer.w_wide is None:                                    # one-off re-tiling of the weights (not capturable)
-                layer.w_wide = torch.empty_like(layer.w)
-                L.check(self.lib.qv2x_conv3x3_i8_pack_wide(C.byref(d), L.ptr(layer.w), L.ptr(layer.w_wide), L.current_stream()), layer.name)
-            L.check(self.lib.qv2x_conv3x3_i8_wide(C.byref(d), L.ptr(x), L.ptr(layer.w_wide), L.ptr(layer.scale), L.ptr(layer.corr),
-                                                  L.ptr(layer.aw), L.ptr(layer.bias), L.ptr(out), L.current_stream()), layer.name)
-            return
-        L.check(self.lib.qv2x_conv3x3_i8(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr),
-                                         L.ptr(layer.aw), L.ptr(layer.bias), L.ptr(out), L.current_stream()), layer.name)
+        launch_conv3x3(self.lib, layer, x, n, h, w, out, out_ctotal=out_ctotal, out_c0=out_c0, wide=self.use_wide_conv)
 
     def _chain(self, ch: _ChainLayers, x, n, h, w, out):
         """``x``: padded input [n][h+2][w+2][64] of the first layer; ``out``: padded output of the last one."""

@@ -18,8 +18,8 @@ import torch
 
 from . import lib as L
 from .camera_encoder import GpuCamHeads, GpuCamStem, stem_shapes
-from .engine import _ConvLayer, capture_call
-from .engine_pyramid import _Conv1x1, _q, bottleneck_layers, launch_conv3x3
+from .engine import _ConvLayer, capture_call, launch_conv3x3
+from .engine_pyramid import _Conv1x1, _q, bottleneck_layers
 from .lift_splat import GpuLiftSplat
 from .ptq_state import CAMERA_TRUNK, check_finite, export_camera_state
 

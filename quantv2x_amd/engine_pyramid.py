@@ -23,7 +23,7 @@ from . import lib as L
 from .ptq_state import CAMERA_PREFIX
 from .camera_bev import center_crop_window, crop_mask_statement, crop_target
 from .engine import (_ConvLayer, _DeconvLayer, _Heads, _dev, _pack_k4p, _pairwise_from_poses, assemble_heter_codes, capture_forward,
-                     codebook_constants, pfn_params, pillar_inputs, scene_layout, split_heads)
+                     codebook_constants, launch_conv3x3, pfn_params, pillar_inputs, scene_layout, split_heads)
 
 
 def _q(state, name):
@@ -153,32 +153,6 @@ class _Block:
                 raise NotImplementedError(f"{name}: a 1x1 shortcut on an fp32 input")
             self.down = _Conv1x1(state, name + ".downsample", in_q, stride, dev)
         self.in_q, self.out_q = in_q, _q(state, name)
-
-
-def launch_conv3x3(lib, layer: _ConvLayer, x, n, h, w, out, out_q, res_mode=0, res=None, res_q=(0.0, 128)):
-    """One 3x3 QuantModule convolution on codes (``qv2x_conv3x3_i8``, its wide form where the shape allows it, or ``_res`` with a fused
-    residual end).  Shared by the Pyramid engine and the camera encoder."""
-    d = L.ConvDesc()
-    d.n, d.h, d.w, d.cin_total, d.stride, d.cout = n, h, w, x.shape[-1], layer.stride, layer.cout
-    d.ngroups = len(layer.groups)
-    for i, (c0, c, zx) in enumerate(layer.groups):
-        d.group_c0[i], d.group_c[i], d.group_zx[i] = c0, c, zx
-    d.out_ctotal, d.out_c0, d.relu = out.shape[-1], 0, 1
-    d.out_delta, d.out_zp = out_q[0], float(out_q[1])
-    st = L.current_stream()
-    if res_mode:
-        L.check(lib.qv2x_conv3x3_i8_res(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
-                                        L.ptr(layer.bias), res_mode, L.ptr(res), int(res_q[1]), float(res_q[0]), L.ptr(out), st), layer.name)
-        return
-    if lib.qv2x_conv3x3_i8_wide_ok(C.byref(d)):
-        if layer.w_wide is None:
-            layer.w_wide = torch.empty_like(layer.w)
-            L.check(lib.qv2x_conv3x3_i8_pack_wide(C.byref(d), L.ptr(layer.w), L.ptr(layer.w_wide), st), layer.name)
-        L.check(lib.qv2x_conv3x3_i8_wide(C.byref(d), L.ptr(x), L.ptr(layer.w_wide), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
-                                         L.ptr(layer.bias), L.ptr(out), st), layer.name)
-        return
-    L.check(lib.qv2x_conv3x3_i8(C.byref(d), L.ptr(x), L.ptr(layer.w), L.ptr(layer.scale), L.ptr(layer.corr), L.ptr(layer.aw),
-                                L.ptr(layer.bias), L.ptr(out), st), layer.name)
 
 
 def launch_conv1x1(lib, layer: _Conv1x1, x, n, h, w, out, mode, out_q=None, res=None, res_q=(0.0, 128)):
